@@ -18,11 +18,12 @@ Launching.  `python bench.py --gpus N` with N > 1 and no torchrun environment st
 file, one process per GPU, RCCL); under an external torchrun (RANK / WORLD_SIZE in the environment) it joins
 that job.  The world size actually joined is what `n_gpus` reports.
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (the bf16 MFMA weight-streaming GEMM of the
-decode step, timed live with HIP events on the engine's stream in a separate profiled pass), "roofline_attn" (KV-cache
-bytes / decode-attention time, same pass), "roofline_decode" (RQ-VAE decoder conv FLOPs / decode time of the timed region),
-"step_frac_of_mfma_peak" (all algorithmic FLOPs of a step / step time / 2.5 PF), "verified" (post-timed-region check of
-the sampled codes), "batch_sweep" (the same measurement at the per-GPU batches SURVEY 8d names: 64 = BASELINE configs[3]
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the JSON line; the line's "roofline_decode" (RQ-VAE
+decoder conv FLOPs / decode time of the timed region) and "step_frac_of_mfma_peak" (all algorithmic FLOPs of a step / step time /
+2.5 PF) are arithmetic on those steps.  With --full it then measures and checks everything else, as extra objects on the line:
+"roofline" for the dominant kernel (the bf16 MFMA weight-streaming GEMM of the decode step, timed live with HIP events on the
+engine's stream in a separate profiled pass), "roofline_attn" (KV-cache bytes / decode-attention time, same pass), "verified"
+(post-timed-region check of the sampled codes), "batch_sweep" (the same measurement at the per-GPU batches SURVEY 8d names: 64 = BASELINE configs[3]
 per-GPU share, 100 / 200 / 500 = the reference's Fig. 4; each with its own roofline and the reference script's
 one-image-per-call loop as "driver_loop"), "per_image_decode" (that loop on its own), "per_image_recon", "roofline_rq"
 (the residual quantiser), "rqvae_encode" (codes/sec) and "cpu_baseline" (the REFERENCE's own modules -- oracle/_ref -- on the
@@ -58,6 +59,7 @@ DEFAULT_BATCH = {'huge': 10752, 'large': 10752, 'small': 10752, 'medium': 16384,
 # batch-sharded the same way), so their multi-GPU default is that per-GPU share; the 1.4B headline model keeps its N = 1 batch on
 # every rank (weak scaling: per-GPU work fixed, so the driver's per-N values are comparable with the N = 1 line).
 DEFAULT_BATCH_MULTI = {'xhuge': 64, 'txt3900m': 64}
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: all files together
 WORKLOADS = {'huge': 'BASELINE configs[2]', 'medium': 'BASELINE configs[1]', 'xhuge': 'BASELINE configs[3] dims',
              'txt3900m': 'BASELINE configs[4] dims', 'cc3m': 'CC-3M 654M'}
 
@@ -73,13 +75,13 @@ def parse_args(argv=None):
     # BASELINE.json configs[2]: top-k=1024 / top-p=0.95 (0 / 1.0 = the reference defaults top_k=None, top_p=None)
     ap.add_argument('--top-k', type=int, default=1024)
     ap.add_argument('--top-p', type=float, default=0.95)
-    ap.add_argument('--sweep', type=str, default='64,100,200,500', help='extra per-GPU batches measured after the timed region ("" = none)')
+    ap.add_argument('--sweep', type=str, default='64,100,200,500', help='with --full: extra per-GPU batches measured after the timed region ("" = none)')
     ap.add_argument('--formats', type=int, default=1,
-                    help='1 (default): after everything else, time the 1.4B model at 2048 images with the default bf16 engine, the opt-in 8-bit key / '
+                    help='with --full, 1 (default): after everything else, time the 1.4B model at 2048 images with the default bf16 engine, the opt-in 8-bit key / '
                          'key + value caches (RQAMD_KV=int8k / int8kv) and the fp16 build of the engine (sample(amp=True)) -> "kv_cache_formats"; 0: skip (~25 s)')
     ap.add_argument('--also', type=str, default='xhuge:64,txt3900m:64',
-                    help='model:batch points measured after everything else on rank 0 at N = 1 (default: the two models BASELINE.json quotes on '
-                         '8 GPUs, at their per-GPU share of 64 images; "" = none).  Adds ~40 s to a default run: after the headline model is '
+                    help='with --full: model:batch points measured after everything else on rank 0 at N = 1 (default: the two models BASELINE.json quotes on '
+                         '8 GPUs, at their per-GPU share of 64 images; "" = none).  Adds ~40 s to a --full run: after the headline model is '
                          'released, two ~3.8B-parameter models are built (random init), captured and timed; a failure is reported in the JSON '
                          'line AND on stderr')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -88,7 +90,18 @@ def parse_args(argv=None):
     ap.add_argument('--overlap-prio', type=int, default=0, help='with --overlap: 1 = sampling stream at high priority, 2 = decode stream at high priority')
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU/gloo rehearsal of the launcher, sharding, gather and timing logic with synthetic pixels (no kernels run; tests only)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run everything else the benchmark measures or checks: the post-run check of the codes, '
+                         'the rooflines (profiled passes), --sweep, the per-image decode / recon loops, the encoder and quantiser, the CPU '
+                         'baseline, --also and --formats.  Without it a run sets up, warms up, times --steps steps, writes --dump-outputs '
+                         'and prints the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (codes, and the [0,1] pixels) as DIR/<name>.npy in float32 / float64, '
+                         f'at most {DUMP_BUDGET_BYTES >> 20} MB in all: an array too large for its share is written as a fixed, seeded '
+                         'sample of its rows')
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.top_k is not None and args.top_k <= 0:
         args.top_k = None
     if args.top_p is not None and args.top_p >= 1.0:
@@ -154,6 +167,28 @@ def one_step(vae, ar, empty_sample, empty_cond, distenv, top_k, top_p):
     if distenv is not None and distenv.world_size > 1:
         pixels = gather_pixels(distenv, pixels)
     return codes, pixels
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: each (name, tensor) of `arrays` -> out_dir/<name>.npy, floating tensors as float32, integer ones (codes) as
+    float64.  Every array gets an equal share of `budget`; one that does not fit it is written as a sample of its rows, drawn by a
+    numpy generator seeded with `seed` from the row count alone, in ascending order -- the same arguments give the same rows.
+    Returns what was written (for the result line)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays:
+        dt = np.float32 if t.is_floating_point() else np.float64
+        n = t.shape[0]
+        row_bytes = (t[0].numel() if n else 0) * np.dtype(dt).itemsize
+        k = n if n * row_bytes <= share else max(1, share // row_bytes)
+        if k < n:
+            rows = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.detach().cpu().numpy().astype(dt)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = {'shape': list(a.shape), 'dtype': a.dtype.name, 'rows': 'all' if k == n else f'{k} of {n}, seeded sample (seed {seed})'}
+    return written
 
 
 def cpu_baseline_reference(model, top_k, top_p, batch=32, positions=16, n_dec=8, threads=16):
@@ -649,10 +684,11 @@ def dry_run(args, rank, world, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
+        dumped = dump_outputs(args.dump_outputs, [('pixels', pixels)]) if args.dump_outputs else None
         print(json.dumps({'metric': 'dry-run (no kernels): launcher / sharding / gather / timing rehearsal', 'value': world * B * args.steps / elapsed,
                           'unit': 'images/sec', 'n_gpus': world, 'world_size': world, 'requested_gpus': args.gpus, 'steps': args.steps,
                           'warmup': args.warmup, 'ms_per_step': elapsed * 1e3 / args.steps, 'higher_is_better': True, 'scaling': 'weak',
-                          'vs_baseline': None, 'dtype': 'none', 'data': 'dry-run', 'gather_rank_major_ok': all(checks),
+                          'vs_baseline': None, 'dtype': 'none', 'data': 'dry-run', 'gather_rank_major_ok': all(checks), 'dump_outputs': dumped,
                           'config': {'workload': 'dry-run', 'batch_per_gpu': B, 'global_batch': B * world}}), flush=True)
     if world > 1:
         dist.barrier()
@@ -752,10 +788,11 @@ def main(argv=None):
                     if distenv is not None:
                         pixels = gather_pixels(distenv, pixels)
                     pixels.record_stream(s_dec)
-                    del pixels
+                    if i < args.steps:
+                        del pixels                           # (the last step's pixels are kept for --dump-outputs)
             prev = cur
         torch.cuda.synchronize(device)
-    for _ in range(0 if args.overlap else args.steps):
+    for step in range(0 if args.overlap else args.steps):
         ev[0].record()
         codes = ar.sample(empty_sample, model_aux=vae, cond=empty_cond, top_k=args.top_k, top_p=args.top_p)
         ev[1].record()
@@ -767,7 +804,8 @@ def main(argv=None):
         ev[2].synchronize()
         t_ar += ev[0].elapsed_time(ev[1])
         t_dec += ev[1].elapsed_time(ev[2])
-        del pixels                                           # the gathered images (world x 6.4 GB) are freed before the next step
+        if step < args.steps - 1:
+            del pixels                                       # the gathered images (world x 6.4 GB) are freed before the next step
     sync()
     elapsed = time.perf_counter() - t0
     rank_times = [elapsed]
@@ -779,9 +817,16 @@ def main(argv=None):
         rank_times = [float(x.item()) for x in allt]
         elapsed = max(rank_times)
 
-    # ---- correctness of what the timed region produced (codes of its last step), after the clock stopped
+    # ---- what the last timed step returned to its caller: the codes and the [0,1] pixels (all ranks' after the gather)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, [('codes', codes), ('pixels', pixels)])
+    del pixels
+
+    # ---- everything below the headline runs with --full only
+    # correctness of what the timed region produced (codes of its last step), after the clock stopped
     verify = None
-    if rank == 0 and not args.overlap and not args.no_profile and args.steps > 0:
+    if args.full and rank == 0 and not args.overlap and not args.no_profile:
         try:
             verify = verify_codes(vae, ar, codes, empty_cond, args.top_k, args.top_p)
         except Exception as e:
@@ -789,7 +834,7 @@ def main(argv=None):
 
     # ---- roofline of the dominant kernel at the timed batch
     roofline = roofline_attn = None
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         roofline, roofline_attn = gemm_roofline(ar, vae, empty_sample, empty_cond, args.top_k, args.top_p, device, args.model, B, cfg)
 
     # ---- what the board lets the matrix pipes do at all: MFMAs alone (no LDS, no memory), once with constant operands (the instruction
@@ -812,7 +857,7 @@ def main(argv=None):
 
     # ---- the same measurement at smaller per-GPU batches (BASELINE configs[3] per-GPU share, reference Fig. 4 batch)
     sweep = []
-    if rank == 0 and world == 1 and args.sweep:
+    if args.full and rank == 0 and world == 1 and args.sweep:
         for b in [int(x) for x in args.sweep.split(',') if x]:
             if b == B:
                 continue
@@ -834,7 +879,7 @@ def main(argv=None):
 
     # ---- per-image decode (the drivers' call pattern), BASELINE's second metric (codes/sec) and the quantiser roofline
     pid = pir = enc = rqr = None
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         pid = per_image_decode(vae, ar, device)
         pir = per_image_recon(vae, device)
         xb = torch.randn((256, 3, 256, 256), device=device).clamp(-1, 1)
@@ -859,7 +904,7 @@ def main(argv=None):
                                           'FLOPs); kernel shares: profiles/r06_encode_kernel_stats.md'}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             try:
                 cpu = cpu_baseline_reference(args.model, args.top_k, args.top_p)
@@ -876,7 +921,7 @@ def main(argv=None):
     # of those configurations would run.  Random-init weights of the named architecture, like the headline.  The headline model and its
     # 180-GB KV cache are released first.
     also = []
-    if rank == 0 and world == 1 and args.also and args.model == 'huge' and not args.overlap:
+    if args.full and rank == 0 and world == 1 and args.also and args.model == 'huge' and not args.overlap:
         try:
             del empty_sample, empty_cond
             if getattr(ar, '_engine', None) is not None:
@@ -907,7 +952,7 @@ def main(argv=None):
     # ---- the opt-in 8-bit key cache next to the default bf16 one ("report both ways"), same model, one moderate batch, measured live;
     # the headline batch both ways: profiles/r05_kv_int8k_ab.txt.  Engines read RQAMD_KV when they are created.
     kv_formats = None
-    if rank == 0 and world == 1 and args.formats and args.model == 'huge' and not args.overlap and os.environ.get('RQAMD_KV', 'bf16') == 'bf16':
+    if args.full and rank == 0 and world == 1 and args.formats and args.model == 'huge' and not args.overlap and os.environ.get('RQAMD_KV', 'bf16') == 'bf16':
         kv_formats = []
         kv_before = os.environ.get('RQAMD_KV')
         try:
@@ -938,7 +983,7 @@ def main(argv=None):
     # ---- the opt-in fp16 RQ-VAE engine (RQAMD_VAE=fp16: same kernels, IEEE fp16 storage; tests/test_gpu_parity.py::test_vae_fp16_engine has its
     # parity) next to the bf16 default: decode_code of 1024 code maps, measured live
     vae_formats = None
-    if rank == 0 and world == 1 and args.formats and not args.overlap and os.environ.get('RQAMD_VAE', 'bf16') == 'bf16':
+    if args.full and rank == 0 and world == 1 and args.formats and not args.overlap and os.environ.get('RQAMD_VAE', 'bf16') == 'bf16':
         vae_formats = []
         vae_before = os.environ.get('RQAMD_VAE')
         try:
@@ -998,7 +1043,7 @@ def main(argv=None):
             # BASELINE.json publishes no number for this metric (`published: {}`): null, as the contract says.  The one figure of the
             # reference that exists -- Fig. 4, batch 500, one A100, fp32 -- is set against batch_sweep's 500 entry (`vs_reference_fig4`)
             'vs_baseline': None,
-            'dtype': 'bf16', 'data': 'synthetic',
+            'dtype': 'bf16', 'data': 'synthetic', 'full': bool(args.full), 'dump_outputs': dumped,
             'config': {'workload': f'RQ-Transformer {args.model} ({WORKLOADS.get(args.model, args.model)}) sampling 8x8x4 codes + RQ-VAE decode; '
                                    f'random-init weights, zero condition',
                        'batch_per_gpu': B, 'global_batch': B * world, 'batch_note': batch_note, 'top_k': args.top_k, 'top_p': args.top_p,

@@ -13,10 +13,11 @@ unset RQ_LIB
 echo "== barrier timeline (new kernel)"
 timeout 300 python scripts/conv_trace.py 2>&1 | tail -16 | cut -c1-600
 echo "== bench (2 steps, full batch)"
-timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --sweep "" 2>&1 | tail -1 > gpurun_out/r03z_bench.json
-python - <<'PY'
-import json
-d=json.load(open('gpurun_out/r03z_bench.json'))
+J=$(mktemp)
+timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sweep "" 2>&1 | tail -1 > $J
+python - $J <<'PY'
+import json, sys
+d=json.load(open(sys.argv[1]))
 print({k:d.get(k) for k in ('value','ms_per_step','ar_ms_per_image','decode_ms_per_image','verified')})
 for k in ('roofline','roofline_decode','roofline_attn'):
     r=d.get(k) or {}

@@ -9,10 +9,11 @@ for lib in base new; do
 done
 unset RQ_LIB
 echo "== bench (2 steps, full batch)"
-timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --sweep "" 2>&1 | tail -1 > gpurun_out/r03w_bench.json
-python - <<'PY'
-import json
-d=json.load(open('gpurun_out/r03w_bench.json'))
+J=$(mktemp)
+timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sweep "" 2>&1 | tail -1 > $J
+python - $J <<'PY'
+import json, sys
+d=json.load(open(sys.argv[1]))
 print({k:d.get(k) for k in ('value','ms_per_step','ar_ms_per_image','decode_ms_per_image','verified')})
 for k in ('roofline','roofline_decode','roofline_attn'):
     r=d.get(k) or {}

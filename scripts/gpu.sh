@@ -3,7 +3,7 @@
 #   gpurun --timeout 900 -- 'bash scripts/gpu.sh tests bench'
 # Tasks (any order, run left to right; outputs under gpurun_out/<TAG>_*):
 #   tests            pytest -m gpu (+ smoke)
-#   bench [args]     python bench.py  (RQ_BENCH_ARGS="--steps 2 ..." for arguments)
+#   bench [args]     python bench.py  (RQ_BENCH_ARGS="--steps 2 ..." for arguments; "--full" for the whole line)
 #   trace            rocprofv3 --kernel-trace --stats of one bench step -> <TAG>_kernel_stats.md
 #   pmc              FETCH_SIZE / WRITE_SIZE of the decode GEMM shapes at RQ_M rows (separate passes) -> <TAG>_gemm_traffic_m<M>.json
 #   ktrace           rocprofv3 --kernel-trace --stats of "$RQ_PMC_CMD" -> <TAG>_ktrace.md

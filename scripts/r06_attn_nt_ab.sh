@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 for rep in 1 2; do
   for lib in "" rq-vae-transformer_amd/variants/librqamd_attn_nt.so; do
-    RQ_LIB=$lib python scripts/bench_with_lib.py --steps 2 --warmup 1 --sweep "" --also "" --formats 0 --no-cpu-baseline 2>/dev/null | python -c "
+    RQ_LIB=$lib python scripts/bench_with_lib.py --full --steps 2 --warmup 1 --sweep "" --also "" --formats 0 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

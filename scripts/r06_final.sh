@@ -7,7 +7,7 @@ R=$PWD
 export RQ_TAG=r06
 bash scripts/gpu.sh tests
 for m in 10752 500 64; do RQ_M=$m bash scripts/gpu.sh pmc > /dev/null 2>&1; ls gpurun_out/r06_gemm_traffic_m$m.json; done
-bash scripts/gpu.sh bench | cut -c1-1500
+RQ_BENCH_ARGS=--full bash scripts/gpu.sh bench | cut -c1-1500
 RQ_TAG=r06_b10752 bash scripts/gpu.sh trace > /dev/null 2>&1; head -24 gpurun_out/r06_b10752_kernel_stats.md
 RQ_TAG=r06_b64 RQ_TRACE_ARGS="--batch 64 --steps 2" bash scripts/gpu.sh trace > /dev/null 2>&1; head -8 gpurun_out/r06_b64_kernel_stats.md
 RQ_TAG=r06_b500 RQ_TRACE_ARGS="--batch 500 --steps 3" bash scripts/gpu.sh trace > /dev/null 2>&1; head -8 gpurun_out/r06_b500_kernel_stats.md

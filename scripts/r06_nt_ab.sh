@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 V=rq-vae-transformer_amd/variants
 for rep in 1 2; do
   for lib in "" ${RQ_VARIANTS:-$V/librqamd_attn_st.so $V/librqamd_smp_nt.so $V/librqamd_conv_nt1.so $V/librqamd_conv_nt2.so}; do
-    RQ_LIB=$lib python scripts/bench_with_lib.py --steps 2 --warmup 1 --sweep "" --also "" --formats 0 --no-cpu-baseline 2>/dev/null | python -c "
+    RQ_LIB=$lib python scripts/bench_with_lib.py --full --steps 2 --warmup 1 --sweep "" --also "" --formats 0 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

@@ -89,3 +89,14 @@ def test_bench_gpus2_self_launch_dry_run():
     assert out['config']['global_batch'] == 8
     one = _run_bench(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4', '--dry-run'])
     assert one['n_gpus'] == 1
+
+
+def test_bench_dry_run_dump_outputs(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned to rank 0: with 2 ranks, the gathered pixels of both, rank-major."""
+    import numpy as np
+    out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '4', '--dry-run', '--dump-outputs', str(tmp_path)])
+    assert out['dump_outputs'] == {'pixels': {'shape': [8, 3, 4, 4], 'dtype': 'float32', 'rows': 'all'}}
+    assert os.listdir(tmp_path) == ['pixels.npy']
+    pix = np.load(tmp_path / 'pixels.npy')
+    assert pix.dtype == np.float32
+    assert np.allclose(pix[:, 0, 0, 0], [r + b / 1000.0 for r in range(2) for b in range(4)])

@@ -168,6 +168,29 @@ def test_bench_gather_plan_and_multi_gpu_defaults():
     assert bench.DEFAULT_BATCH_MULTI == {'xhuge': 64, 'txt3900m': 64} and 'huge' not in bench.DEFAULT_BATCH_MULTI
 
 
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: floating outputs as float32, integer codes as float64 (exact); an array over its share of the budget is
+    written as a seeded sample of its rows, ascending -- the same rows on every call -- and all files together stay within the budget."""
+    import bench
+    codes = torch.randint(0, 16384, (40, 2, 2, 4))
+    pixels = torch.rand((1000, 3, 8, 8))
+    budget = 200 * 1024
+    outs = []
+    for name in ('a', 'b'):
+        d = tmp_path / name
+        info = bench.dump_outputs(str(d), [('codes', codes), ('pixels', pixels)], budget=budget)
+        assert sorted(os.listdir(d)) == ['codes.npy', 'pixels.npy']
+        outs.append((info, np.load(d / 'codes.npy'), np.load(d / 'pixels.npy')))
+    info, c, p = outs[0]
+    assert c.dtype == np.float64 and np.array_equal(c, codes.numpy().astype(np.float64)) and info['codes']['rows'] == 'all'
+    assert p.dtype == np.float32 and 1 <= p.shape[0] < 1000 and p.shape[1:] == (3, 8, 8) and info['pixels']['shape'] == list(p.shape)
+    assert c.nbytes + p.nbytes <= budget
+    flat = pixels.numpy().reshape(1000, -1)
+    rows = [int(np.flatnonzero((flat == r.reshape(-1)).all(1))[0]) for r in p]
+    assert rows == sorted(set(rows))                                        # distinct rows of the output, ascending
+    assert outs[1][0] == info and np.array_equal(outs[1][1], c) and np.array_equal(outs[1][2], p)
+
+
 def test_read_ahead_torch_attributes():
     """RQVAE's read-ahead behind per-row calls (rqvae/models/rqvae/rqvae.py: _ReadAhead) recognises "row i of the batch the previous call
     saw" through two PRIVATE torch attributes: `Tensor._base` (a view's base tensor) and `Tensor._version` (bumped by in-place edits).
