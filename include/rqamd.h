@@ -237,7 +237,10 @@ int rqamd_dbg_gemm_bf16(const void* A, const void* W, int M, int N, int K, const
                         void* out, int bm, int bn, int splitk, void* stream);
 /* One raw implicit-GEMM convolution launch (the conv form of the same kernel): x NHWC bf16
  * [B][H>>ups][W>>ups][Cin] (H, W = virtual input size after the folded nearest-2x upsample), w bf16
- * [Cout][k][k][Cin], out NHWC bf16 (+bias, +resid if not NULL); stride 2 = Downsample (layers.py:50-54). */
+ * [Cout][k][k][Cin], out NHWC bf16 (+bias, +resid if not NULL); stride 2 = Downsample (layers.py:50-54).
+ * flags bit 0: skip the epilogue (ablation); bits 8..12: virtual split-K count (the K loop as that many chunks, each summed
+ * from zero and added in chunk order -- what the engine runs on its <= 32^2 convs of many images; 0 or 1 = none; the count
+ * must leave an even number of K-tiles per chunk). */
 int rqamd_dbg_conv_bf16(const void* x, const void* w, const float* bias, const void* resid, int B, int H, int W,
                         int Cin, int Cout, int ksize, int stride, int ups, void* out, int bm, int bn, int flags,
                         void* stream);

@@ -376,6 +376,17 @@ static int vae_prepare_slab(rqamd_vae* h, int B) {
     return RQAMD_OK;
 }
 
+// The slab of a two-phase call (below): phase 1 runs super-chunks of ns images and a tail of batch % ns, phase 2 chunks of `chunk`
+// images out of them, and each of these calls of <= SPLIT_MAX_B images divides K over workgroups -- so the slab is sized for the largest
+// of them, not for `chunk` alone (RQAMD_VAE_CHUNK=1, 6 images: the 16^2 512 -> 512 conv of the 6-image super-chunk needs 37.7 MB of
+// slab where one image reserves 33.5).
+static int vae_prepare_slab_two_phase(rqamd_vae* h, int batch, int chunk, int ns) {
+    int b = 0;
+    for (const int m : {ns, batch % ns, chunk, ns % chunk, (batch % ns) % chunk})
+        if (m <= rqamd_vae::SPLIT_MAX_B && m > b) b = m;
+    return b ? vae_prepare_slab(h, b) : RQAMD_OK;
+}
+
 // Two-phase calls (round 6).  The layers at <= 16^2 (implicit-GEMM convs over a few hundred rows per image, single-head attention,
 // GroupNorm passes) run at 0.18-0.32 of the MFMA peak on the 128 images of a chunk and 1.8 x faster on 256 and more
 // (scripts/conv_lowres_tiles.py); the chunk itself cannot grow, it is what bounds the 256^2 tensors.  So a call of more than one chunk
@@ -608,6 +619,7 @@ extern "C" int rqamd_vae_decode(rqamd_vae* h, const float* z_q, int batch, float
         const int ns = vae_super_chunk(h, batch, true, &spi);
         if (ns > chunk) {
             RQ_TRY(h->stage.reserve((size_t)ns * spi));
+            RQ_TRY(vae_prepare_slab_two_phase(h, batch, chunk, ns));
             for (int s0 = 0; s0 < batch; s0 += ns) {
                 const int m = (batch - s0 < ns) ? batch - s0 : ns;
                 RQ_TRY(decode_chunk(h, z_q + (size_t)s0 * lowres * lowres * c.embed_dim, m, nullptr, (hipStream_t)stream, 1, h->stage.as<bf16_t>()));
@@ -646,6 +658,7 @@ extern "C" int rqamd_vae_encode(rqamd_vae* h, const float* x, int batch, float* 
         const int ns = vae_super_chunk(h, batch, false, &spi);
         if (ns > chunk) {
             RQ_TRY(h->stage.reserve((size_t)ns * spi));
+            RQ_TRY(vae_prepare_slab_two_phase(h, batch, chunk, ns));
             for (int s0 = 0; s0 < batch; s0 += ns) {
                 const int m = (batch - s0 < ns) ? batch - s0 : ns;
                 for (int b0 = 0; b0 < m; b0 += chunk) {

@@ -503,7 +503,8 @@ extern "C" int rqamd_dbg_gemm_bf16(const void* A, const void* W, int M, int N, i
 }
 
 // diagnostics: one implicit-GEMM convolution launch.  x NHWC bf16 [B][H>>ups][W>>ups][Cin], w [Cout][k][k][Cin] bf16,
-// out NHWC bf16 [B][Ho][Wo][Cout] (+bias, +resid when given).  flags bit0: skip the epilogue (ablation).
+// out NHWC bf16 [B][Ho][Wo][Cout] (+bias, +resid when given).  flags bit0: skip the epilogue (ablation); bits 8..12: virtual split-K
+// count (GemmArgs::vsplit; 0 or 1 = none) -- taken out of the flags before they reach GemmArgs::dbg.
 extern "C" int rqamd_dbg_conv_bf16(const void* x, const void* w, const float* bias, const void* resid, int B, int H, int W,
                                    int Cin, int Cout, int ksize, int stride, int ups, void* out, int bm, int bn, int flags,
                                    void* stream) {
@@ -514,7 +515,7 @@ extern "C" int rqamd_dbg_conv_bf16(const void* x, const void* w, const float* bi
     a.A = (const bf16_t*)x; a.W = (const bf16_t*)w; a.M = B * Ho * Wo; a.N = Cout; a.K = ksize * ksize * Cin; a.lda = Cin;
     a.conv = 1; a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = Ho; a.Wout = Wo; a.ksize = ksize; a.stride = stride; a.pad = pad; a.ups = ups;
     a.epi = resid ? EPI_BF16_RESID : EPI_BF16; a.bias = bias; a.out = out; a.ldo = Cout; a.resid = (const bf16_t*)resid; a.ldr = Cout;
-    a.splitk = 1; a.dbg = flags;
+    a.splitk = 1; a.vsplit = (flags >> 8) & 31; a.dbg = flags & ~(31 << 8);
     if (bm <= 0) bm = a.M >= 128 ? 128 : 64;
     if (bn <= 0) bn = (Cout % 128 == 0) ? 128 : 64;
     return rq_gemm_launch(a, bm, bn, (hipStream_t)stream);

@@ -915,6 +915,37 @@ def test_emu_gemm_stream(nat):
     assert np.array_equal(nat.dbg_gemm(a, w, bias, epi=1, bm=66, bn=64, splitk=1).float().numpy(), out)
 
 
+def test_emu_dbg_conv(nat):
+    """The implicit-GEMM conv through rqamd_dbg_conv_bf16 (the MODE 1 / 2 gather of gemm.h) at tiny shapes: stride 2 with the reference's
+    (0, 1, 0, 1) pad, 3x3 stride 1, the folded nearest upsample, the residual epilogue and the virtual split-K of flags bits 8..12 --
+    vs fp64 with the strict elementwise bounds of tests/kernel_check.py; outputs inside NaN guards, operands with NaN rows behind them."""
+    import kernel_check as kc
+    g = torch.Generator().manual_seed(8)
+    # (B, Hs, Ws, Cin, Cout, stride, ups, resid, vsplit, tiles)
+    cases = [(2, 8, 6, 64, 64, 2, 0, False, 1, ((64, 64), (128, 64))),
+             (1, 6, 10, 128, 128, 1, 0, True, 1, ((64, 128), (128, 128))),
+             (1, 6, 10, 128, 128, 1, 0, True, 3, ((64, 128), (256, 128))),
+             (2, 3, 4, 64, 64, 1, 1, False, 1, ((64, 64),)),
+             (1, 3, 4, 128, 128, 1, 1, True, 3, ((128, 128),))]
+    for (B, Hs, Ws, Cin, Cout, stride, ups, with_res, vs, tiles) in cases:
+        H, W = Hs << ups, Ws << ups
+        Ho, Wo = (H // 2, W // 2) if stride == 2 else (H, W)
+        x = kc.poisoned(torch.randn((B, Hs, Ws, Cin), generator=g).to(torch.bfloat16), 1)
+        w = kc.poisoned((torch.randn((Cout, 3, 3, Cin), generator=g) / (9 * Cin) ** 0.5).to(torch.bfloat16), 3)
+        bias = torch.randn((Cout,), generator=g)
+        resid = kc.poisoned(torch.randn((B, Ho, Wo, Cout), generator=g).to(torch.bfloat16), 1) if with_res else None
+        ref, S, _ = kc.conv_ref(x, w, bias, resid=resid, stride=stride, ups=ups)
+        for (bm, bn) in tiles:
+            what = f'B={B} {H}x{W} {Cin}->{Cout} stride {stride} ups {ups} resid {with_res} vsplit {vs} tile {bm}x{bn}'
+            buf, out = kc.guarded((B, Ho, Wo, Cout), torch.bfloat16, 'cpu')
+            nat.dbg_conv(x, w, bias, resid, ksize=3, stride=stride, ups=ups, bm=bm, bn=bn, flags=vs << 8, out=out)
+            kc.check_guard(buf, out.numel(), what)
+            kc.check_bf16(out.reshape(-1, Cout), ref, S, kc.steps(9 * Cin, vs, 2 if with_res else 1), kc.C['conv'], what=what)
+    x = torch.randn((1, 6, 10, 128), generator=g).to(torch.bfloat16)
+    with pytest.raises(ValueError):                                    # 18 K-tiles: 2 chunks of 9 (odd)
+        nat.dbg_conv(x, w, None, ksize=3, bm=128, bn=128, flags=2 << 8)
+
+
 def test_emu_conv_halo(nat):
     """halo-reuse 3x3 conv (csrc/conv_halo.hip): plain, with fused GroupNorm+SiLU on the input, with residual, one and two
     channel chunks; against the oracle's conv2d / silu on the bf16-rounded operands."""
