@@ -198,6 +198,19 @@ int rqamd_rqt_logits(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, in
  * when block_size_cond <= 1). */
 int rqamd_rqt_forward(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
                       const float* const* codebooks, float* logits_out, float* cond_logits_out, void* stream);
+/* RQTransformer.forward (transformers.py:113-188) in ONE pass over all positions; outputs as rqamd_rqt_forward.  Every code is
+ * given, so the body stack runs once over (image, token) rows and the head stack once over (image, position, depth) rows with
+ * cache-free causal attention; no KV cache is used.  The work is chunked by rows (rqamd_rqt_set_option "fwd.chunk_rows", default
+ * 4096) in a workspace of its own: captured sampling graphs of the handle stay valid.  Same arithmetic as the stepped entry points;
+ * results differ from theirs by the GEMM tile choice only. */
+int rqamd_rqt_forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
+                              const float* const* codebooks, float* logits_out, float* cond_logits_out, void* stream);
+/* log p(code) of every code under the same pass: logp_out (batch,H,W,D) fp32 = log_softmax(logits)[code], reduced from
+ * sub-chunks of logits rows in the workspace -- (batch,H,W,D,vocab) is never materialised.  cond_logp_out (batch,
+ * block_size_cond-1) fp32 = log p(cond[t+1] | cond[:t+1]) under cond_classifier, or NULL (must be NULL when block_size_cond <= 1;
+ * needs cond).  A code outside 0..vocab-1 gives NaN. */
+int rqamd_rqt_log_probs(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
+                        const float* const* codebooks, float* logp_out, float* cond_logp_out, void* stream);
 /* Stepping form of rqamd_rqt_sample for callers that draw the samples themselves -- e.g. torch.multinomial on the filtered
  * probabilities, which consumes the device generator exactly as the reference's sample_from_logits does
  * (rqvae/utils/utils.py:112; RQTransformer.sample transformers.py:346-364 is this loop):

@@ -15,6 +15,10 @@
 //    every position and can be captured once as a hipGraph and replayed H*W-1 times; the sampler has
 //    no host synchronisation (the reference syncs once per step, rqvae/utils/utils.py:103).
 //  * weights are bf16 (fp32 accumulate, fp32 residual stream / LayerNorm / softmax / logits).
+//
+// Teacher-forced passes (RQTransformer.forward, transformers.py:113-188) exist in two forms: the same stepping over given codes
+// (rqamd_rqt_logits / rqamd_rqt_forward: B rows per launch, the kernels sampling uses) and ONE pass over all positions
+// (forward_onepass below: rqamd_rqt_forward_onepass / rqamd_rqt_log_probs, no KV cache, a workspace of its own).
 #include <string.h>
 #include <string>
 #include <vector>
@@ -99,6 +103,11 @@ struct rqamd_rqt {
     const float* step_pend_slabs = nullptr;        // the body's last fc2 partials, consumed by depth 0 of the same position
     int step_pend_n = 0;
     const float* step_pend_bias = nullptr;
+
+    // one-pass teacher-forced forward (forward_onepass): a workspace of its own, sized by a row budget per chunk -- never h->ws / h->kv,
+    // whose addresses the captured sampling graphs hold
+    int fwd_chunk_rows = 4096;    // "fwd.chunk_rows": body rows per chunk of images, head rows per sub-chunk
+    DevBuf fws;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -223,6 +232,11 @@ extern "C" int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value) {
             return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_set_option: embed_dim=%d must be a multiple of head.n_head=%d with head_dim <= 256", h->E, value);
         for (auto& L : h->head) L.nh = value;
         h->gvalid = false;                       // captured graphs hold the old launches
+        return RQAMD_OK;
+    }
+    if (strcmp(name, "fwd.chunk_rows") == 0) {   // row budget of the one-pass forward's chunks (tests force several chunks on a tiny model)
+        if (value < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: fwd.chunk_rows = %d < 1", value);
+        h->fwd_chunk_rows = value;
         return RQAMD_OK;
     }
     return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: unknown option '%s'", name);
@@ -454,9 +468,14 @@ struct Pending { const float* slabs; int n; const float* bias; };   // un-reduce
 // one transformer block on `rows` single-token rows; x is the fp32 residual stream (updated lazily:
 // `pend` carries the previous block's fc2 partials + bias into this block's first resid_ln)
 struct PrefillCtx { int img0, n_img, P; };   // non-null: `rows` = n_img * P prefix tokens of images img0.. (multi-token causal attention)
+// one-pass forward, non-null: `rows` = n_seq sequences of T consecutive rows, causal attention inside each, no KV cache.
+// packed: the head stack's depth groups (T <= 8, a lane per query); else the body stack's (image, token) rows (a lane per query of a
+// wavefront per (image, head), K / V staged in LDS)
+struct OnePassCtx { int n_seq, T; bool packed; };
 
 static int run_block(rqamd_rqt* h, RqtLayer& L, float* x_in, float* x, Pending& pend, const float* addvec, int rows,
-                     const int* step, int step_off, int t_max, int Tcap, hipStream_t st, const PrefillCtx* pf = nullptr) {
+                     const int* step, int step_off, int t_max, int Tcap, hipStream_t st, const PrefillCtx* pf = nullptr,
+                     const OnePassCtx* op = nullptr) {
     const int E = h->E;
     ResidLnArgs r{};
     r.x_in = x_in; r.slabs = pend.slabs; r.n_slabs = pend.n; r.bias = pend.bias; r.addvec = addvec;
@@ -464,7 +483,15 @@ static int run_block(rqamd_rqt* h, RqtLayer& L, float* x_in, float* x, Pending& 
     r.gamma = L.ln1w; r.beta = L.ln1b; r.y = h->y; r.rows = rows; r.E = E; r.eps = 1e-5f;
     RQ_TRY(rq_launch_resid_ln(r, st));
     RQ_TRY(step_gemm(h, h->y, E, L.wqkv, rows, 3 * E, E, EPI_BF16, L.bqkv, nullptr, 0, h->qkv, 3 * E, nullptr, st));
-    if (pf) {
+    if (op && op->packed) {
+        AttnPackedArgs ak{};
+        ak.qkv = h->qkv; ak.y = h->ya; ak.rows = rows; ak.group = op->T; ak.nh = L.nh; ak.E = E;
+        RQ_TRY(rq_launch_attn_packed(ak, st));
+    } else if (op) {
+        AttnPrefillArgs ap{};                      // kc == null: the cache-free form
+        ap.qkv = h->qkv; ap.y = h->ya; ap.n_img = op->n_seq; ap.P = op->T; ap.nh = L.nh; ap.E = E; ap.Tcap = op->T;
+        RQ_TRY(rq_launch_attn_prefill(ap, st));
+    } else if (pf) {
         AttnPrefillArgs ap{};
         const long img_stride = (long)E * Tcap;
         ap.qkv = h->qkv; ap.y = h->ya;
@@ -759,6 +786,203 @@ extern "C" int rqamd_rqt_forward(rqamd_rqt* h, const int64_t* codes, const int64
     StepCtx c{};
     c.B = batch; c.codebooks = codebooks; c.temperature = 1.f; c.sample = false; c.logits_out = logits_out; c.cond_logits_out = cond_logits_out;
     return run_all(h, c, codes, cond, 0, false, nullptr, (hipStream_t)stream);
+}
+
+// -------------------------------------------------------------------------------------------------
+// One-pass teacher-forced forward: RQTransformer.forward (transformers.py:113-188) the way the reference computes it -- every code is
+// known, so the body stack runs ONCE over (image, token) rows and the head stack once over (image, position, depth) rows, instead of
+// 64 cached steps that each stream the whole weight set.  Same kernels and arithmetic as the stepped path (run_block's GEMMs and
+// resid_ln; embeddings, attention and classifier as position_body / position_depth form them), so the two differ by GEMM tile choice
+// only.  Work is chunked by rows: a chunk of images whose body rows fit fwd_chunk_rows, and inside it head sub-chunks of whole
+// positions within the same budget; the head rows' order IS the order of the logits, so the classifier writes into logits_out.
+// logp form: the classifier writes sub-chunks of rows into a workspace buffer of ~48 MB that log_prob_kernel reduces to one number
+// per row -- (B,H,W,D,V) never exists.  No KV cache is read, written or allocated, and h->ws / h->kv are not touched.
+struct OnePassOut {
+    float* logits;       // (B,HW,D,V) or null
+    float* cond_logits;  // (B, cond_len-1, vocab_size_cond) or null
+    float* logp;         // (B,HW,D) or null
+    float* cond_logp;    // (B, cond_len-1) or null
+};
+
+// the workspace pointers run_block works on, swapped for the duration of a one-pass call (restored on every exit path)
+struct WorkspaceSwap {
+    rqamd_rqt* h;
+    float *x, *xh, *slabs;
+    bf16_t *y, *qkv, *ya, *hbuf, *ain;
+    explicit WorkspaceSwap(rqamd_rqt* h_) : h(h_), x(h_->x), xh(h_->xh), slabs(h_->slabs), y(h_->y), qkv(h_->qkv), ya(h_->ya), hbuf(h_->hbuf), ain(h_->ain) {}
+    ~WorkspaceSwap() { h->x = x; h->xh = xh; h->slabs = slabs; h->y = y; h->qkv = qkv; h->ya = ya; h->hbuf = hbuf; h->ain = ain; }
+};
+
+static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int B, const float* const* codebooks,
+                           const OnePassOut& o, hipStream_t st) {
+    h->step_on = false;                            // ends a stepping sequence like any other call
+    RQ_TRY(finalize_tables(h, st));
+    const int E = h->E, V = h->V, D = h->D, HW = h->HW, Tb = h->Tbody, P = h->cond_len - 1;
+    const int vc = h->cfg.vocab_size_cond < 1 ? 1 : h->cfg.vocab_size_cond;
+    const bool want_cond = o.cond_logits || o.cond_logp;
+    if (want_cond && (!h->w_ccls || h->n_ccls_seen < 4)) return rq_fail(RQAMD_ERR_STATE, "rqt: cond_classifier parameters not set");
+    // chunk geometry
+    int n_img = h->fwd_chunk_rows / Tb;            // images per body chunk
+    if (n_img < 1) n_img = 1;
+    if (n_img > B) n_img = B;
+    long n_grp = h->fwd_chunk_rows / D;            // (image, position) groups per head sub-chunk
+    if (n_grp < 1) n_grp = 1;
+    if (n_grp > (long)n_img * HW) n_grp = (long)n_img * HW;
+    const size_t rb = (size_t)n_img * Tb, rh = (size_t)n_grp * D, rows = rb > rh ? rb : rh;
+    // logits sub-chunk of the logp forms: ~48 MB of fp32 rows, whole depth groups (BatchLinear runs one GEMM per depth over it)
+    long cls_grp = (long)((48u << 20) / ((size_t)V * 4)) / D;
+    if (cls_grp < 1) cls_grp = 1;
+    if (cls_grp > n_grp) cls_grp = n_grp;
+    long ccls_rows = (long)((48u << 20) / ((size_t)vc * 4));
+    if (ccls_rows < 1) ccls_rows = 1;
+    if (ccls_rows > (long)n_img * (P > 0 ? P : 1)) ccls_rows = (long)n_img * (P > 0 ? P : 1);
+    size_t lg_bytes = 0;
+    if (o.logp) lg_bytes = (size_t)cls_grp * D * V * 4;
+    if (o.cond_logp && (size_t)ccls_rows * vc * 4 > lg_bytes) lg_bytes = (size_t)ccls_rows * vc * 4;
+    const size_t total = al(rb * E * 4) + al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
+                         + al(rows * 4 * E * 2) + al(rows * h->Din * 2) + al(lg_bytes);
+    RQ_TRY(h->fws.reserve(total));
+    WorkspaceSwap keep(h);
+    char* p = (char*)h->fws.p;
+    auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
+    h->x = (float*)take(rb * E * 4); h->xh = (float*)take(rows * E * 4);
+    h->slabs = (float*)take((size_t)h->max_slabs * rows * E * 4);
+    h->y = (bf16_t*)take(rows * E * 2); h->ya = (bf16_t*)take(rows * E * 2);
+    h->qkv = (bf16_t*)take(rows * 3 * E * 2); h->hbuf = (bf16_t*)take(rows * 4 * E * 2);
+    h->ain = (bf16_t*)take(rows * h->Din * 2);
+    float* lg = (float*)take(lg_bytes);
+
+    for (int b0 = 0; b0 < B; b0 += n_img) {
+        const int n = B - b0 < n_img ? B - b0 : n_img;
+        const int64_t* ccodes = codes + (long)b0 * HW * D;
+        const int64_t* ccond = cond ? cond + (long)b0 * h->cond_len : nullptr;
+        const int brows = n * Tb;
+        // ---- body input: conditioning tokens + the embeddings of spatial positions 0 .. HW-2 (transformers.py:127-137)
+        BodyInputArgs bi{};
+        bi.cond = ccond; bi.cond_stride = h->cond_len; bi.cond_len = h->cond_len; bi.vocab_cond = vc; bi.cond_emb = h->cond_emb; bi.pos_cond = h->pos_cond;
+        bi.bias_tab = h->body_in_bias; bi.pos_tab = h->pos_hw; bi.n_img = n; bi.HW = HW; bi.D = D; bi.E = E; bi.x = h->x;
+        if (h->in_vq) {
+            if (HW > 1) {
+                GatherCodesArgs g{};
+                g.codes = ccodes; g.head = 0; g.cumsum = 1; g.row0 = 0; g.rows = n * (HW - 1); g.HW = HW; g.D = D; g.dim = h->Din; g.out = h->ain;
+                for (int d = 0; d < D; ++d) { g.cb[d] = codebooks[d]; g.K[d] = h->Vd[d]; }
+                RQ_TRY(rq_launch_gather_codes(g, st));
+                RQ_TRY(step_gemm(h, h->ain, h->Din, h->w_in, g.rows, E, h->Din, EPI_F32, nullptr, nullptr, 0, h->xh, E, nullptr, st));
+            }
+            bi.emb = h->xh;
+        } else {
+            bi.codes = ccodes; bi.table = h->tok_emb;
+            for (int d = 0; d < D; ++d) { bi.offs[d] = h->tok_offs[d]; bi.V[d] = h->Vd[d]; }
+        }
+        RQ_TRY(rq_launch_body_input(bi, st));
+        // ---- body stack over (image, token) rows
+        Pending pend{nullptr, 0, nullptr};
+        const OnePassCtx bctx{n, Tb, false};
+        h->cur_gelu_v2 = h->cfg.gelu_v2 == 1 || h->cfg.gelu_v2 == 3;
+        for (auto& L : h->body) RQ_TRY(run_block(h, L, h->x, h->x, pend, nullptr, brows, nullptr, 0, 0, Tb, st, nullptr, &bctx));
+        if (pend.slabs || pend.bias) {             // the last fc2's partials (+ bias) into the stream: both heads read it row by row
+            ResidLnArgs r{};
+            r.x_in = h->x; r.x_out = h->x; r.slabs = pend.slabs; r.n_slabs = pend.n; r.bias = pend.bias; r.rows = brows; r.E = E; r.eps = 1e-5f;
+            RQ_TRY(rq_launch_resid_ln(r, st));
+        }
+        // ---- cond_classifier over the body outputs of tokens 0 .. cond_len-2 (transformers.py:150-153)
+        if (want_cond && P > 0) {
+            for (long r0 = 0; r0 < (long)n * P; r0 += ccls_rows) {
+                const int nr = (int)((long)n * P - r0 < ccls_rows ? (long)n * P - r0 : ccls_rows);
+                HeadInputArgs hi{};                // (rows (image, t < P) of the stream, gathered: "depth 0" rows of groups of one, nothing added)
+                hi.xbody = h->x; hi.Tb = Tb; hi.tok0 = 0; hi.HW = P; hi.D = 1; hi.E = E; hi.row0 = r0; hi.rows = nr; hi.xh = h->xh; hi.pos_d = nullptr;
+                RQ_TRY(rq_launch_head_input(hi, st));
+                ResidLnArgs r{};
+                r.x_in = h->xh; r.gamma = h->ccls_lnw; r.beta = h->ccls_lnb; r.y = h->y; r.rows = nr; r.E = E; r.eps = 1e-5f;
+                RQ_TRY(rq_launch_resid_ln(r, st));
+                float* dst = o.cond_logits ? o.cond_logits + ((long)b0 * P + r0) * vc : lg;
+                RQ_TRY(step_gemm(h, h->y, E, h->w_ccls, nr, vc, E, EPI_F32, h->b_ccls, nullptr, 0, dst, vc, nullptr, st));
+                if (o.cond_logp) {                 // log p(cond[t + 1] | cond[: t + 1])
+                    if (!cond) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: cond_logp_out without cond");
+                    LogProbArgs lp{};
+                    lp.logits = dst; lp.ld = vc; lp.rows = nr; lp.V = vc; lp.targets = ccond; lp.row0 = r0; lp.t_per = P; lp.t_stride = h->cond_len; lp.t_off = 1;
+                    lp.out = o.cond_logp + (long)b0 * P + r0;
+                    RQ_TRY(rq_launch_log_prob(lp, st));
+                }
+            }
+        }
+        // ---- head stack over (image, position, depth) rows, sub-chunks of whole positions
+        const long groups = (long)n * HW;
+        for (long g0 = 0; g0 < groups; g0 += n_grp) {
+            const long ng = groups - g0 < n_grp ? groups - g0 : n_grp;
+            const int hrows = (int)(ng * D);
+            HeadInputArgs hi{};
+            hi.xbody = h->x; hi.Tb = Tb; hi.tok0 = h->cond_len - 1; hi.bias_tab = h->head_in_bias; hi.pos_d = h->pos_d;
+            hi.row0 = g0 * D; hi.rows = hrows; hi.HW = HW; hi.D = D; hi.E = E; hi.xh = h->xh;
+            if (h->head_vq) {
+                if (D > 1) {
+                    GatherCodesArgs g{};
+                    g.codes = ccodes; g.head = 1; g.cumsum = h->cumsum ? 1 : 0; g.row0 = g0 * D; g.rows = hrows; g.HW = HW; g.D = D; g.dim = h->Din; g.out = h->ain;
+                    for (int d = 0; d < D; ++d) { g.cb[d] = codebooks[d]; g.K[d] = h->Vd[d]; }
+                    RQ_TRY(rq_launch_gather_codes(g, st));
+                        RQ_TRY(step_gemm(h, h->ain, h->Din, h->w_headin, hrows, E, h->Din, EPI_F32, nullptr, nullptr, 0, h->xh, E, nullptr, st));
+                }
+            } else {
+                hi.codes = ccodes; hi.table = h->tok_emb;
+                for (int d = 0; d < D; ++d) { hi.offs[d] = h->tok_offs[d]; hi.V[d] = h->Vd[d]; }
+            }
+            RQ_TRY(rq_launch_head_input(hi, st));
+            Pending hp{nullptr, 0, nullptr};
+            const OnePassCtx hctx{(int)ng, D, true};
+            h->cur_gelu_v2 = h->cfg.gelu_v2 == 1 || h->cfg.gelu_v2 == 2;
+            for (auto& L : h->head) RQ_TRY(run_block(h, L, h->xh, h->xh, hp, nullptr, hrows, nullptr, 0, 0, D, st, nullptr, &hctx));
+            ResidLnArgs r{};
+            r.x_in = h->xh; r.slabs = hp.slabs; r.n_slabs = hp.n; r.bias = hp.bias;
+            r.gamma = h->cls_lnw; r.beta = h->cls_lnb; r.y = h->y; r.rows = hrows; r.E = E; r.eps = 1e-5f;
+            RQ_TRY(rq_launch_resid_ln(r, st));
+            // classifier: the shared matrix over all rows, or BatchLinear's matrix of each depth over that depth's rows (stride D).
+            // Teacher-forced logits are not LogitMask-ed (see position_depth).
+            const long row_g = ((long)b0 * HW + g0) * D;       // first row of this sub-chunk in the outputs
+            const long step_g = o.logits ? ng : cls_grp;
+            for (long c0 = 0; c0 < ng; c0 += step_g) {
+                const long cg = ng - c0 < step_g ? ng - c0 : step_g;
+                float* dst = o.logits ? o.logits + (row_g + c0 * D) * V : lg;
+                const bf16_t* A = h->y + c0 * D * E;
+                if (h->shared_cls) {
+                    RQ_TRY(step_gemm(h, A, E, h->w_cls, (int)(cg * D), V, E, EPI_F32, h->b_cls, nullptr, 0, dst, V, nullptr, st));
+                } else {
+                    for (int d = 0; d < D; ++d)
+                        RQ_TRY(step_gemm(h, A + (long)d * E, D * E, h->w_cls + (long)d * V * E, (int)cg, V, E, EPI_F32, h->b_cls + (long)d * V, nullptr, 0,
+                                         dst + (long)d * V, D * V, nullptr, st));
+                }
+                if (o.logp) {
+                    LogProbArgs lp{};
+                    lp.logits = dst; lp.ld = V; lp.rows = (int)(cg * D); lp.V = V; lp.targets = codes; lp.row0 = row_g + c0 * D; lp.t_per = 1; lp.t_stride = 1; lp.t_off = 0;
+                    lp.out = o.logp + row_g + c0 * D;
+                    RQ_TRY(rq_launch_log_prob(lp, st));
+                }
+            }
+        }
+    }
+    return RQAMD_OK;
+}
+
+extern "C" int rqamd_rqt_forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
+                                         const float* const* codebooks, float* logits_out, float* cond_logits_out, void* stream) {
+    if (!h || !codes || !codebooks || !logits_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_forward_onepass: null argument");
+    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_forward_onepass: batch < 1");
+    if (cond_logits_out && h->cond_len <= 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_forward_onepass: cond_logits need block_size_cond > 1");
+    if (h->seen.size() - h->n_ccls_seen < h->n_required)
+        return rq_fail(RQAMD_ERR_STATE, "rqt: only %zu of %zu parameters set", h->seen.size() - h->n_ccls_seen, h->n_required);
+    const OnePassOut o{logits_out, cond_logits_out, nullptr, nullptr};
+    return forward_onepass(h, codes, cond, batch, codebooks, o, (hipStream_t)stream);
+}
+
+extern "C" int rqamd_rqt_log_probs(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
+                                   const float* const* codebooks, float* logp_out, float* cond_logp_out, void* stream) {
+    if (!h || !codes || !codebooks || !logp_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: null argument");
+    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: batch < 1");
+    if (cond_logp_out && h->cond_len <= 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: cond_logp needs block_size_cond > 1");
+    if (cond_logp_out && !cond) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: cond_logp_out without cond");
+    if (h->seen.size() - h->n_ccls_seen < h->n_required)
+        return rq_fail(RQAMD_ERR_STATE, "rqt: only %zu of %zu parameters set", h->seen.size() - h->n_ccls_seen, h->n_required);
+    const OnePassOut o{nullptr, nullptr, logp_out, cond_logp_out};
+    return forward_onepass(h, codes, cond, batch, codebooks, o, (hipStream_t)stream);
 }
 
 // ---- lanes (round 6): a second handle that runs on the SAME parameter arena as `src` -- its own workspace, KV caches, graphs and

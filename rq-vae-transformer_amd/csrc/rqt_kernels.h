@@ -11,6 +11,10 @@
 //                          (transformers.py:109-111,218-225,249-257), only for the NEW position
 //   cond_embed_kernel   <- cond_emb(cond) + pos_emb_cond (transformers.py:224)
 //   sample_kernel       <- sample_from_logits (rqvae/utils/utils.py:82-123), no host sync
+//   one-pass forward    <- RQTransformer.forward (transformers.py:113-188) over all positions at once: gather_codes_kernel /
+//                          body_input_kernel / head_input_kernel (the inputs of the two stacks, :127-137,:160-175), attn_prefill_kernel
+//                          without a cache (body), attn_packed_kernel (depth groups of the head stack), log_prob_kernel
+//                          (F.cross_entropy's log_softmax + gather, :371-381, one number per logits row)
 #pragma once
 #include "rq_hip.h"
 
@@ -46,7 +50,8 @@ struct AttnDecodeArgs {
 // runs the whole prefix through MultiSelfAttention.forward with the causal mask, attentions.py:60-104).
 struct AttnPrefillArgs {
     const bf16_t* qkv;      // [n_img * P][3E], row = img * P + i (token i of image img)
-    bf16_t* kc;             // K cache of the FIRST image of this chunk: [n_img][nh][Tcap][64]; positions 0..P-1 are written
+    bf16_t* kc;             // K cache of the FIRST image of this chunk: [n_img][nh][Tcap][64]; positions 0..P-1 are written.  Null (with vc, ksc,
+                            // vsc): the cache-free form of the one-pass teacher-forced forward -- nothing is appended anywhere
     bf16_t* vc;
     float* ksc;             // as AttnDecodeArgs::ksc (of the first image of the chunk), or null
     float* vsc;             // as AttnDecodeArgs::vsc, or null
@@ -113,5 +118,77 @@ int rq_launch_mask_logits(float* logits, int rows, int V, int v_lo, hipStream_t 
 int rq_launch_cvt_bf16(const float* src, bf16_t* dst, long n, hipStream_t s);
 // dst[c][r] = bf16(src[r][c]): BatchLinear's (in, out) matrices into the GEMM's K-contiguous weight layout
 int rq_launch_cvt_bf16_transpose(const float* src, bf16_t* dst, int R, int Cc, hipStream_t s);
+// ---- one-pass teacher-forced forward (engine_rqt.hip: forward_onepass): every position of a chunk of images at once.
+// Body rows are ordered (image, token), head rows (image, position, depth) -- the order of the logits.
+
+// codebook rows summed over depth -> bf16 GEMM operand, for all rows of a chunk (embed_tokens_kernel for one position at a time):
+//   body (head == 0): row R = (image, q), q = 0 .. HW-2: sum over all depths of the codes at spatial position q
+//   head (head == 1): row R = (g, d), g = image * HW + position: sum over depths [cumsum ? 0 : d-1, d) of the codes at g (d == 0: zeros)
+struct GatherCodesArgs {
+    const int64_t* codes;   // [n_img][HW][D] codes of the chunk
+    const float* cb[8];     // per-depth codebooks (K, dim), padding row excluded
+    int K[8];
+    int head, cumsum;
+    long row0;              // first row of this launch (rows are counted from the start of the chunk)
+    int rows, HW, D, dim;
+    bf16_t* out;            // [rows][dim]
+};
+int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s);
+
+// body input rows (image, t), t = 0 .. Tb-1: t < cond_len: cond_emb[cond[image][t]] + pos_emb_cond[t]; else, with q = t - cond_len:
+// emb[(image, q)] + bias_tab[q] (emb = the input_mlp GEMM over GatherCodesArgs rows), or -- table non-null -- pos_tab[q] + sum_d table[offs[d] + code_d]
+struct BodyInputArgs {
+    const int64_t* cond;    // [n_img][cond_stride] or null (class 0)
+    int cond_stride, cond_len, vocab_cond;
+    const float *cond_emb, *pos_cond;
+    const float* emb;       // [n_img * (HW-1)][E] or null
+    const float* bias_tab;  // [HW][E] (body_in_bias)
+    const int64_t* codes;   // [n_img][HW][D] (learned token embeddings only)
+    const float* table;     // [sum V][E] or null
+    int offs[8], V[8];
+    const float* pos_tab;   // [HW][E] (pos_emb_hw)
+    int n_img, HW, D, E;
+    float* x;               // [n_img * Tb][E], Tb = cond_len - 1 + HW
+};
+int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s);
+
+// head input rows (g, d): d == 0: body output of token cond_len-1 + position of the image + pos_emb_d[0]; d >= 1: xh (holding the
+// head_mlp GEMM over GatherCodesArgs rows) += bias_tab[d], or -- table non-null -- pos_d[d] + table[offs[d-1] + code_{d-1}]
+struct HeadInputArgs {
+    const float* xbody;     // [n_img * Tb][E]
+    int Tb, tok0;           // tok0 = cond_len - 1
+    const float* bias_tab;  // [D][E] (head_in_bias)
+    const float* pos_d;     // [D][E]; null with D == 1: a plain gather of rows tok0 .. tok0 + HW - 1 of every image (cond_classifier input)
+    const int64_t* codes;   // [n_img][HW][D] (learned token embeddings only)
+    const float* table;
+    int offs[8], V[8];
+    long row0;
+    int rows, HW, D, E;
+    float* xh;              // [rows][E]
+};
+int rq_launch_head_input(const HeadInputArgs& a, hipStream_t s);
+
+// causal attention inside groups of `group` <= 8 consecutive rows (the depth axis of the head stack): one lane per (row, head), the
+// group's keys / values straight from the qkv rows; same arithmetic as the decode kernels
+struct AttnPackedArgs {
+    const bf16_t* qkv;      // [rows][3E]
+    bf16_t* y;              // [rows][E]
+    int rows, group, nh, E; // rows % group == 0
+};
+int rq_launch_attn_packed(const AttnPackedArgs& a, hipStream_t s);
+
+// out[r] = logits[r][target] - logsumexp(logits[r][:]) in fp32; target = targets[(R / t_per) * t_stride + R % t_per + t_off], R = row0 + r
+// (NaN where the target is outside 0 .. V-1)
+struct LogProbArgs {
+    const float* logits;    // [rows][ld]
+    long ld;
+    int rows, V;
+    const int64_t* targets;
+    long row0;
+    int t_per, t_stride, t_off;
+    float* out;             // [rows]
+};
+int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s);
+
 int rq_launch_set_int(int* p, int v, hipStream_t s);
 int rq_launch_add_int(int* p, int v, hipStream_t s);

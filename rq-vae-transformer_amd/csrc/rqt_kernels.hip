@@ -735,6 +735,8 @@ __global__ __launch_bounds__(64) void attn_generic_decode_kernel(AttnDecodeArgs 
 
 // conditioning prefix (AttnPrefillArgs as attn_prefill_kernel): one wavefront per (image, head, token i); keys / values 0..i straight from
 // the qkv rows of the image, token i's own pair appended to the cache at position i
+// APPEND = false (one-pass teacher-forced forward): nothing is written to a cache (p.kc / p.vc are null)
+template <bool APPEND>
 __global__ __launch_bounds__(64) void attn_generic_prefill_kernel(AttnPrefillArgs p) {
     __shared__ float sQ[256], sP[264];
     const int lane = threadIdx.x;
@@ -745,9 +747,11 @@ __global__ __launch_bounds__(64) void attn_generic_prefill_kernel(AttnPrefillArg
     const bf16_t* q0 = p.qkv + (long)img * p.P * 3 * p.E + hh * hd;       // token 0 of the image, this head
     const bf16_t* q = q0 + (long)i * 3 * p.E;
     const bf16_t *k = q + p.E, *v = q + 2 * p.E;
-    bf16_t* kc = p.kc + (pair * p.Tcap + i) * hd;
-    bf16_t* vc = p.vc + (pair * p.Tcap + i) * hd;
-    for (int d = lane; d < hd; d += 64) { kc[d] = k[d]; vc[d] = v[d]; }
+    if (APPEND) {
+        bf16_t* kc = p.kc + (pair * p.Tcap + i) * hd;
+        bf16_t* vc = p.vc + (pair * p.Tcap + i) * hd;
+        for (int d = lane; d < hd; d += 64) { kc[d] = k[d]; vc[d] = v[d]; }
+    }
     attn_generic_core(q, q0 + p.E, 3L * p.E, q0 + 2 * p.E, 3L * p.E, i, k, v, p.y + ((long)img * p.P + i) * p.E + hh * hd, hd, lane, sQ, sP);
 }
 
@@ -808,6 +812,9 @@ int rq_launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
 // reads the same K / V row at a time (LDS broadcast, conflict-free).  Same arithmetic as the decode kernels above: bf16
 // q / k / v, fp32 dot products, scale 1/8, fp32 softmax weights on bf16 values, one bf16 rounding of the output.
 // The prefix is processed once per sample() call (the decode kernels run 64 times), P <= 255, so this is a VALU kernel.
+// APPEND = false is the cache-free form of the one-pass teacher-forced forward (engine_rqt.hip: forward_onepass): P = every body token
+// of the image, K and V come from the qkv rows alone and no cache pointer is touched (p.kc / p.vc are null).
+template <bool APPEND>
 __global__ __launch_bounds__(64) void attn_prefill_kernel(AttnPrefillArgs p) {
     RQ_DYN_SMEM(smem);
     const int lane = threadIdx.x;
@@ -827,7 +834,8 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(AttnPrefillArgs p) {
         const bool in = idx < P * 8;                  // whole 8-lane groups: P * 8 is a multiple of 8
         const int j = in ? idx >> 3 : P - 1, c = idx & 7;
         const rq_u128 kv = ld128(q0 + (long)j * 3 * E + E + c * 8), vv = ld128(q0 + (long)j * 3 * E + 2 * E + c * 8);
-        if (ksc) {                                    // uniform: opt-in 8-bit key cache (the prefix attention itself runs on the bf16 keys)
+        if (!APPEND) {
+        } else if (ksc) {                             // uniform: opt-in 8-bit key cache (the prefix attention itself runs on the bf16 keys)
             float s_app;
             const rq_u64w kb = quant_key_chunk(kv, s_app);
             if (in) {
@@ -837,7 +845,8 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(AttnPrefillArgs p) {
         } else if (in) {
             st128(kc + j * 64 + c * 8, kv);
         }
-        if (vsc) {                                    // uniform: opt-in 8-bit value cache (likewise: the prefix attention runs on the bf16 values)
+        if (!APPEND) {
+        } else if (vsc) {                             // uniform: opt-in 8-bit value cache (likewise: the prefix attention runs on the bf16 values)
             float s_app;
             const rq_u64w vb = quant_key_chunk(vv, s_app);
             if (in) {
@@ -903,17 +912,22 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(AttnPrefillArgs p) {
 }
 
 int rq_launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s) {
+    const bool append = a.kc != nullptr;            // no cache: the one-pass teacher-forced forward
+    if (!append && (a.vc || a.ksc || a.vsc)) return rq_fail(RQAMD_ERR_INVALID, "prefill attention: cache-free form with a cache pointer");
+    if (append && !a.vc) return rq_fail(RQAMD_ERR_INVALID, "prefill attention: key cache without a value cache");
     if (a.nh >= 1 && a.E != a.nh * 64) {            // any other head size: the plain kernel
         RQ_TRY(attn_generic_check(a.E, a.nh, a.Tcap, a.ksc));
         if (a.P < 1 || a.P > a.Tcap) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %d tokens (cache %d)", a.P, a.Tcap);
         const long blocks = (long)a.n_img * a.nh * a.P;
         if (blocks > 0x7fffffffL) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %ld (image, head, token) triples", blocks);
-        RQ_LAUNCH(attn_generic_prefill_kernel, dim3((unsigned)blocks), dim3(64), 0, s, a);
+        if (append) RQ_LAUNCH(attn_generic_prefill_kernel<true>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+        else RQ_LAUNCH(attn_generic_prefill_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, s, a);
         return rq_check_launch("attn_generic_prefill_kernel");
     }
     if (a.nh < 1 || a.P < 1 || a.P > a.Tcap || a.P > 255) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %d tokens (cache %d, max 255)", a.P, a.Tcap);
     const size_t smem = (size_t)a.P * 64 * 2 * 2;
-    RQ_LAUNCH(attn_prefill_kernel, dim3((unsigned)(a.n_img * a.nh)), dim3(64), smem, s, a);
+    if (append) RQ_LAUNCH(attn_prefill_kernel<true>, dim3((unsigned)(a.n_img * a.nh)), dim3(64), smem, s, a);
+    else RQ_LAUNCH(attn_prefill_kernel<false>, dim3((unsigned)(a.n_img * a.nh)), dim3(64), smem, s, a);
     return rq_check_launch("attn_prefill_kernel");
 }
 
@@ -1708,4 +1722,261 @@ extern "C" int rqamd_sample_logits(const float* logits, int rows, int vocab, flo
     a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.probs_out = probs_out; a.D = 1;
     a.redo = row_flags;     // caller-owned (rows ints) or NULL: without it every row takes the general kernel
     return rq_launch_sample(a, (hipStream_t)stream);
+}
+
+// =================================================================================================
+// One-pass teacher-forced forward (engine_rqt.hip: forward_onepass): every code is known up front, so the body stack runs once over
+// (image, token) rows and the head stack once over (image, position, depth) rows.  The kernels below form the inputs of the two
+// stacks for all rows at once (the same arithmetic as embed_tokens_kernel / tok_embed_kernel / cond_embed_kernel one position at a
+// time), attend inside the depth groups of the head rows, and reduce logits rows to log-probabilities.
+__global__ void gather_codes_kernel(GatherCodesArgs p) {
+    const int per_row = p.dim / 8;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)p.rows * per_row) return;
+    const long r = gid / per_row;
+    const int c = (int)(gid - r * per_row);
+    const long R = p.row0 + r;
+    long cpos;
+    int lo, hi;
+    if (p.head) {
+        cpos = R / p.D;
+        hi = (int)(R - cpos * p.D);
+        lo = p.cumsum ? 0 : (hi > 0 ? hi - 1 : 0);
+    } else {
+        const long img = R / (p.HW - 1);
+        cpos = img * p.HW + (R - img * (p.HW - 1));
+        lo = 0; hi = p.D;
+    }
+    const int64_t* codes = p.codes + cpos * p.D;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int d = lo; d < hi; ++d) {
+        const long code = codes[d];
+        if (code < 0 || code >= p.K[d]) continue;                  // padding row (index K) embeds to zero
+        const float* src = p.cb[d] + code * p.dim + c * 8;
+        const f32x4 a = *(const f32x4*)src, bq = *(const f32x4*)(src + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { acc[e] += a[e]; acc[4 + e] += bq[e]; }
+    }
+    rq_u128 o;
+    o.x = pack_bf16x2(acc[0], acc[1]); o.y = pack_bf16x2(acc[2], acc[3]);
+    o.z = pack_bf16x2(acc[4], acc[5]); o.w = pack_bf16x2(acc[6], acc[7]);
+    st128(p.out + r * p.dim + c * 8, o);
+}
+int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s) {
+    if (a.dim % 8 != 0) return rq_fail(RQAMD_ERR_UNSUPPORTED, "embed: dim %d %% 8 != 0", a.dim);
+    if (a.rows < 1) return RQAMD_OK;
+    const long n = (long)a.rows * (a.dim / 8);
+    RQ_LAUNCH(gather_codes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    return rq_check_launch("gather_codes_kernel");
+}
+
+__global__ void body_input_kernel(BodyInputArgs p) {
+    const int per_row = p.E / 4, Tb = p.cond_len - 1 + p.HW;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)p.n_img * Tb * per_row) return;
+    const long row = gid / per_row;
+    const int c = (int)(gid - row * per_row) * 4;
+    const long img = row / Tb;
+    const int t = (int)(row - img * Tb);
+    f32x4 v;
+    if (t < p.cond_len) {
+        long cc = p.cond ? p.cond[img * p.cond_stride + t] : 0;
+        if (cc < 0) cc = 0;
+        if (cc >= p.vocab_cond) cc = p.vocab_cond - 1;
+        v = *(const f32x4*)(p.cond_emb + cc * p.E + c) + *(const f32x4*)(p.pos_cond + (long)t * p.E + c);
+    } else {
+        const int q = t - p.cond_len;
+        if (p.table) {
+            const int64_t* codes = p.codes + (img * p.HW + q) * p.D;
+            v = *(const f32x4*)(p.pos_tab + (long)q * p.E + c);
+            for (int d = 0; d < p.D; ++d) {
+                const long code = codes[d];
+                if (code < 0 || code >= p.V[d]) rq_trap();          // index error in the reference (nn.Embedding)
+                v = v + *(const f32x4*)(p.table + ((long)p.offs[d] + code) * p.E + c);
+            }
+        } else {
+            v = *(const f32x4*)(p.emb + (img * (p.HW - 1) + q) * p.E + c) + *(const f32x4*)(p.bias_tab + (long)q * p.E + c);
+        }
+    }
+    *(f32x4*)(p.x + row * p.E + c) = v;
+}
+int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s) {
+    const long n = (long)a.n_img * (a.cond_len - 1 + a.HW) * (a.E / 4);
+    RQ_LAUNCH(body_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    return rq_check_launch("body_input_kernel");
+}
+
+__global__ void head_input_kernel(HeadInputArgs p) {
+    const int per_row = p.E / 4;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)p.rows * per_row) return;
+    const long r = gid / per_row;
+    const int c = (int)(gid - r * per_row) * 4;
+    const long R = p.row0 + r, g = R / p.D;
+    const int d = (int)(R - g * p.D);
+    float* dst = p.xh + r * p.E + c;
+    if (d == 0) {
+        const long img = g / p.HW;
+        const long brow = img * p.Tb + p.tok0 + (g - img * p.HW);
+        f32x4 v = *(const f32x4*)(p.xbody + brow * p.E + c);
+        if (p.pos_d) v = v + *(const f32x4*)(p.pos_d + c);
+        *(f32x4*)dst = v;
+    } else if (p.table) {
+        const long code = p.codes[g * p.D + d - 1];
+        if (code < 0 || code >= p.V[d - 1]) rq_trap();              // index error in the reference (nn.Embedding)
+        *(f32x4*)dst = *(const f32x4*)(p.pos_d + (long)d * p.E + c) + *(const f32x4*)(p.table + ((long)p.offs[d - 1] + code) * p.E + c);
+    } else {
+        *(f32x4*)dst = *(const f32x4*)dst + *(const f32x4*)(p.bias_tab + (long)d * p.E + c);
+    }
+}
+int rq_launch_head_input(const HeadInputArgs& a, hipStream_t s) {
+    const long n = (long)a.rows * (a.E / 4);
+    RQ_LAUNCH(head_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    return rq_check_launch("head_input_kernel");
+}
+
+// Packed short-sequence causal attention: the head stack's sequences are the D <= 8 depths of one spatial position.  A wavefront per
+// sequence would idle 64 - D lanes, so ONE LANE owns one (row, head) query: 64 / D sequences share a wavefront, no lane talks to
+// another and nothing goes through LDS.  The lane's query and the <= 8 keys / values of its group are read straight from the qkv rows
+// (the D lanes of a group read the same K / V bytes: one fetch from the L2, the rest are L1 hits).  Scores stay in registers
+// (fp32 dot products of the 16-bit operands, scale 1/sqrt(head_dim)), a two-pass fp32 softmax over them, fp32 weights on the 16-bit
+// values, one rounding of the output -- the decode kernels' arithmetic.  HD = 64: the released head size, loops unrolled; HD = 0: any
+// head size that is a multiple of 8, run-time trip counts; VEC = false: any head size, one component at a time.
+template <int HD, bool VEC>
+__global__ __launch_bounds__(256) void attn_packed_kernel(AttnPackedArgs p) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= p.rows) return;
+    const int hh = blockIdx.y, D = p.group;                          // (D <= 8: the score registers below)
+    const int hd = HD ? HD : p.E / p.nh;
+    const long g0 = r - r % D;                                       // first row of the group
+    const int dq = (int)(r - g0);                                     // this query attends keys 0 .. dq
+    const long ld = 3L * p.E;
+    const bf16_t* q = p.qkv + r * ld + hh * hd;
+    const bf16_t* k0 = p.qkv + g0 * ld + p.E + hh * hd;
+    const bf16_t* v0 = k0 + p.E;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    float sc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sc[j] = 0.f;
+    if (VEC) {
+        const int nc = hd / 8;
+#pragma unroll
+        for (int c = 0; c < (HD ? HD / 8 : nc); ++c) {
+            float qf[8];
+            unpack8(ld128(q + c * 8), qf);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (j <= dq) {
+                    float kf[8];
+                    unpack8(ld128(k0 + j * ld + c * 8), kf);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) sc[j] = fmaf(qf[e], kf[e], sc[j]);
+                }
+            }
+        }
+    } else {
+        for (int e = 0; e < hd; ++e) {
+            const float qe = bf16_to_f32(q[e]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j <= dq) sc[j] = fmaf(qe, bf16_to_f32(k0[j * ld + e]), sc[j]);
+        }
+    }
+    const float scale = HD == 64 ? 0.125f : 1.0f / sqrtf((float)hd);
+    float mx = NEG_INF;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sc[j] = (j <= dq) ? sc[j] * scale : NEG_INF;
+        mx = fmaxf(mx, sc[j]);
+    }
+    float l = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        sc[j] = (j <= dq) ? rq_fast_exp2((sc[j] - mx) * 1.4426950408889634f) : 0.f;
+        l += sc[j];
+    }
+    const float inv = 1.0f / l;
+    bf16_t* o = p.y + r * p.E + hh * hd;
+    if (VEC) {
+        const int nc = hd / 8;
+#pragma unroll
+        for (int c = 0; c < (HD ? HD / 8 : nc); ++c) {
+            float acc[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (j <= dq) {
+                    float vf[8];
+                    unpack8(ld128(v0 + j * ld + c * 8), vf);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[e] = fmaf(sc[j], vf[e], acc[e]);
+                }
+            }
+            rq_u128 u;
+            u.x = pack_bf16x2(acc[0] * inv, acc[1] * inv); u.y = pack_bf16x2(acc[2] * inv, acc[3] * inv);
+            u.z = pack_bf16x2(acc[4] * inv, acc[5] * inv); u.w = pack_bf16x2(acc[6] * inv, acc[7] * inv);
+            st128(o + c * 8, u);
+        }
+    } else {
+        for (int e = 0; e < hd; ++e) {
+            float acc = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j <= dq) acc = fmaf(sc[j], bf16_to_f32(v0[j * ld + e]), acc);
+            o[e] = f32_to_bf16(acc * inv);
+        }
+    }
+}
+int rq_launch_attn_packed(const AttnPackedArgs& a, hipStream_t s) {
+    if (a.nh < 1 || a.E % a.nh) return rq_fail(RQAMD_ERR_INVALID, "attention: embed_dim %d is not a multiple of n_head %d", a.E, a.nh);
+    if (a.E / a.nh > 256) return rq_fail(RQAMD_ERR_UNSUPPORTED, "attention: head_dim %d > 256", a.E / a.nh);
+    if (a.group < 1 || a.group > 8 || a.rows < 1 || a.rows % a.group)
+        return rq_fail(RQAMD_ERR_INVALID, "packed attention: %d rows in groups of %d (1 .. 8, whole groups)", a.rows, a.group);
+    if (a.nh > 65535) return rq_fail(RQAMD_ERR_UNSUPPORTED, "packed attention: %d heads", a.nh);
+    const int hd = a.E / a.nh;
+    const dim3 g((unsigned)((a.rows + 255) / 256), (unsigned)a.nh), b(256);
+    if (hd == 64) RQ_LAUNCH((attn_packed_kernel<64, true>), g, b, 0, s, a);
+    else if (hd % 8 == 0) RQ_LAUNCH((attn_packed_kernel<0, true>), g, b, 0, s, a);      // (E is a multiple of 64: every row and head starts on 16 bytes)
+    else RQ_LAUNCH((attn_packed_kernel<0, false>), g, b, 0, s, a);
+    return rq_check_launch("attn_packed_kernel");
+}
+
+// Fused log-softmax + gather: one workgroup per logits row.  Each thread keeps a running (max, sum of exp) over its share of the
+// row -- 16-byte loads when the row allows, one rescale per new maximum -- the four wavefronts combine through wave reductions and
+// eight floats of LDS, and thread 0 writes logit[target] - max - log(sum).  fp32 throughout (expf / logf, not the one-instruction
+// forms: the result is not rounded to 16 bits afterwards).
+__global__ __launch_bounds__(SMP_T) void log_prob_kernel(LogProbArgs p) {
+    __shared__ float red[8];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = p.logits + (long)row * p.ld;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    float m = NEG_INF, sum = 0.f;
+    auto take = [&](float v) {
+        if (v > m) { sum = sum * expf(m - v) + 1.0f; m = v; }       // (first finite value: exp(-inf) = 0)
+        else if (!(v <= NEG_INF)) sum += expf(v - m);                // (-inf adds nothing; a NaN logit makes the row NaN, as log_softmax does)
+    };
+    if ((p.V & 3) == 0 && (p.ld & 3) == 0 && ((uintptr_t)p.logits & 15) == 0) {
+        for (int i = tid * 4; i < p.V; i += SMP_T * 4) {
+            const f32x4 v = *(const f32x4*)(lg + i);
+            take(v[0]); take(v[1]); take(v[2]); take(v[3]);
+        }
+    } else {
+        for (int i = tid; i < p.V; i += SMP_T) take(lg[i]);
+    }
+    const float M = blk_max(m, red);
+    const float S = blk_sum(m > NEG_INF ? sum * expf(m - M) : 0.f, red);
+    if (tid == 0) {
+        const long R = p.row0 + row;
+        const long tg = p.targets[(R / p.t_per) * p.t_stride + R % p.t_per + p.t_off];
+        p.out[row] = (tg >= 0 && tg < p.V) ? (lg[tg] - M) - logf(S) : __int_as_float(0x7fc00000);
+    }
+}
+int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
+    if (a.rows < 1) return RQAMD_OK;
+    if (a.V < 1 || a.t_per < 1) return rq_fail(RQAMD_ERR_INVALID, "log_prob: V = %d, t_per = %d", a.V, a.t_per);
+    RQ_LAUNCH(log_prob_kernel, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
+    return rq_check_launch("log_prob_kernel");
 }

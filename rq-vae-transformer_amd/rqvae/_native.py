@@ -76,6 +76,8 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_forward_onepass': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_log_probs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_set_code': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -604,6 +606,42 @@ class RqtEngine(_Engine):
         self._run(lambda: self._L.rqamd_rqt_forward(self._h, ptr(codes, torch.int64), ptr(cond, torch.int64), B, cbs,
                                                   ptr(out), ptr(cl), stream_of(codes)))
         return out, cl
+
+    # ---- one pass over all positions (rqamd_rqt_forward_onepass / rqamd_rqt_log_probs): no KV cache, a workspace of its own
+    def forward_onepass(self, codes, cond, codebooks):
+        """seq_logits (B,H,W,D,V), or (seq_logits, cond_logits (B, block_size_cond-1, vocab_size_cond)) for text-conditioned models"""
+        self._check(codes, cond, codebooks)
+        B = codes.shape[0]
+        c = self.cfg
+        out = torch.empty((B, c.H, c.W, c.D, c.vocab_size), dtype=torch.float32, device=codes.device)
+        cl = None
+        if c.block_size_cond > 1:
+            cl = torch.empty((B, c.block_size_cond - 1, max(c.vocab_size_cond, 1)), dtype=torch.float32, device=codes.device)
+        cbs = _ptr_array(codebooks[:c.D])
+        self._run(lambda: self._L.rqamd_rqt_forward_onepass(self._h, ptr(codes, torch.int64), ptr(cond, torch.int64), B, cbs,
+                                                          ptr(out), ptr(cl), stream_of(codes)))
+        return out if cl is None else (out, cl)
+
+    def log_probs(self, codes, cond, codebooks):
+        """log p(code) of every code (B,H,W,D) fp32, or (that, log p(cond[t+1] | cond[:t+1]) (B, block_size_cond-1)) for
+        text-conditioned models; the (B,H,W,D,V) logits are never materialised"""
+        self._check(codes, cond, codebooks)
+        B = codes.shape[0]
+        c = self.cfg
+        out = torch.empty((B, c.H, c.W, c.D), dtype=torch.float32, device=codes.device)
+        cl = None
+        if c.block_size_cond > 1:
+            if cond is None:
+                raise ValueError('log_probs of a text-conditioned model needs cond')
+            cl = torch.empty((B, c.block_size_cond - 1), dtype=torch.float32, device=codes.device)
+        cbs = _ptr_array(codebooks[:c.D])
+        self._run(lambda: self._L.rqamd_rqt_log_probs(self._h, ptr(codes, torch.int64), ptr(cond, torch.int64), B, cbs,
+                                                    ptr(out), ptr(cl), stream_of(codes)))
+        return out if cl is None else (out, cl)
+
+    def set_option(self, name, value):
+        """options the config struct does not carry (include/rqamd.h: rqamd_rqt_set_option), e.g. 'fwd.chunk_rows'"""
+        check(self._L.rqamd_rqt_set_option(self._h, name.encode(), int(value)), self._L)
 
     # ---- stepping form: the caller draws the samples (rqamd_rqt_step_*)
     def step_begin(self, partial, cond, codebooks):

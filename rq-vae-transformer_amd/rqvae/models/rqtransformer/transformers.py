@@ -96,6 +96,10 @@ class RQTransformer(Stage2Model):
         self.use_graph = os.environ.get('RQAMD_GRAPH', '1') != '0'
         # 'philox' (default): on-device sampler inside the captured graphs; 'torch': host loop + torch.multinomial (see sample)
         self.sampler = os.environ.get('RQAMD_SAMPLER', 'philox')
+        # how forward() / teacher_forced_logits() run: 'stepped' (default): the cached sampler driven over the given codes, B rows per
+        # launch; 'one_pass' (or RQAMD_FORWARD=one_pass): every position at once, no KV cache (rqamd_rqt_forward_onepass) -- same
+        # arithmetic, other GEMM tiles.  cached_forward and sample (cached or not) always step.
+        self.forward_mode = os.environ.get('RQAMD_FORWARD', 'stepped')
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -236,6 +240,7 @@ class RQTransformer(Stage2Model):
         engine's cached path over the given codes (identical to the uncached pass up to rounding --
         the reference's own cached==uncached invariant, transformers.py:352-356)."""
         self._cf = None                                  # (any other engine call ends a cached_forward sequence)
+        one_pass = self._one_pass()
         if self.block_size_cond > 1:
             # (seq_logits, cond_logits): cond_classifier over the body outputs of the first cond_len-1 positions
             # (transformers.py:150-153,185-186); the engine takes them from the multi-token prefill of the prefix
@@ -247,8 +252,13 @@ class RQTransformer(Stage2Model):
             c = self._cond(cond, B, xs.device)
             if c is None:
                 c = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=xs.device)
-            return self._on_side_stream(xs.device, lambda: eng.forward(codes, c, cbs))
+            return self._on_side_stream(xs.device, lambda: (eng.forward_onepass if one_pass else eng.forward)(codes, c, cbs))
         return self.teacher_forced_logits(xs, model_aux, cond, amp=amp)
+
+    def _one_pass(self):
+        if self.forward_mode not in ('stepped', 'one_pass'):
+            raise ValueError(f"forward_mode = {self.forward_mode!r} ('stepped' or 'one_pass')")
+        return self.forward_mode == 'one_pass'
 
     @torch.no_grad()
     def teacher_forced_logits(self, xs, model_aux=None, cond=None, amp=False):
@@ -260,7 +270,29 @@ class RQTransformer(Stage2Model):
         cbs = self._checked_codebooks(model_aux)
         codes = xs.to(torch.long).contiguous()
         c = self._cond(cond, B, xs.device)
+        if self._one_pass():
+            def run():
+                out = eng.forward_onepass(codes, c, cbs)
+                return out[0] if isinstance(out, tuple) else out
+            return self._on_side_stream(xs.device, run)
         return self._on_side_stream(xs.device, lambda: eng.logits(codes, c, cbs))
+
+    @torch.no_grad()
+    def log_probs(self, xs, model_aux=None, cond=None, amp=False):
+        """log p(code) of every code of `xs` under forward(): (B,H,W,D) fp32 = log_softmax(forward(xs))[..., xs], or (seq_logp,
+        cond_logp (B, block_size_cond-1) = log p(cond[t+1] | cond[:t+1])) when block_size_cond > 1, mirroring what forward() returns
+        there.  Always one pass over all positions; the log-softmax and the gather run on sub-chunks of logits rows inside the
+        engine, so (B,H,W,D,V) is never allocated: -log_probs(xs).mean() is compute_loss(forward(xs), xs) at any batch size."""
+        (B, H, W, D) = xs.shape
+        assert torch.Size([H, W, D]) == self.block_size
+        self._cf = None
+        eng = self._eng(amp)
+        cbs = self._checked_codebooks(model_aux)
+        codes = xs.to(torch.long).contiguous()
+        c = self._cond(cond, B, xs.device)
+        if c is None and self.block_size_cond > 1:
+            raise ValueError('log_probs of a text-conditioned model needs cond (its tokens are the targets of cond_logp)')
+        return self._on_side_stream(xs.device, lambda: eng.log_probs(codes, c, cbs))
 
     @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
@@ -371,3 +403,17 @@ class RQTransformer(Stage2Model):
         if use_soft_target:
             raise NotImplementedError('soft-target cross entropy (RQ-Transformer training) is out of scope')
         return F.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
+
+    def compute_cond_loss(self, cond_logits, conds):
+        """transformers.py:383-391: next-token cross entropy of the conditioning prefix, cond_logits (B, T-1, Vc) against conds[:, 1:]."""
+        assert cond_logits.shape[1] == conds.shape[1] - 1
+        return F.cross_entropy(cond_logits.reshape(-1, cond_logits.shape[-1]), conds[:, 1:].reshape(-1))
+
+    @torch.no_grad()
+    def compute_codebook_loss(self, logits, targets, use_soft_target=False):
+        """transformers.py:393-410: the cross entropy of each depth (codebook) separately, (D,) -- hard targets only."""
+        if use_soft_target:
+            raise NotImplementedError('soft-target cross entropy (RQ-Transformer training) is out of scope')
+        D = logits.shape[-2]
+        per_code = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1), reduction='none')
+        return per_code.reshape(-1, D).mean(dim=0)
