@@ -169,6 +169,9 @@ typedef struct {
     int vocab_sizes[8];       /* per-depth vocabulary (all equal to vocab_size unless shared_* are off); vocab_size = max */
 } rqamd_rqt_config;
 
+/* Longest body context, H * W + block_size_cond - 1 tokens: 32 x 32 positions behind 64 text tokens (1087).  Contexts beyond 256 tokens
+ * need head size 64 in the body stack and the bf16 / fp16 KV cache (RQAMD_KV unset); rqamd_rqt_create refuses everything else. */
+#define RQAMD_RQT_MAX_CONTEXT 1088
 int rqamd_rqt_create(const rqamd_rqt_config* cfg, rqamd_rqt** out);
 int rqamd_rqt_destroy(rqamd_rqt* h);
 /* options of a handle that the config struct does not carry (ABI v7).  "head.n_head" <- head.block.n_head where it differs from

@@ -88,7 +88,8 @@ struct rqamd_rqt {
     bool kv_int8v = false;   // RQAMD_KV=int8kv: the body-stack values likewise (round 6)
 
     // graph cache
-    // one captured position per 8-key bucket of the body context (the attention kernel variant is baked in)
+    // one captured position per 8-key bucket of the body context (the attention kernel variant is baked in); the last one is the catch-all of
+    // contexts beyond 256 tokens: captured once with t_max = Tbody - 1, it serves every position from token 256 on (position_body)
     static constexpr int NGRAPH = 33;
     hipGraphExec_t gexec[NGRAPH] = {};
     struct Key { int B; float T; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey;
@@ -147,7 +148,19 @@ extern "C" int rqamd_rqt_create(const rqamd_rqt_config* c, rqamd_rqt** out) {
     h->E = c->embed_dim; h->HW = c->H * c->W; h->D = c->D; h->V = c->vocab_size; h->Din = c->input_embed_dim;
     h->cond_len = c->block_size_cond < 1 ? 1 : c->block_size_cond;
     h->Tbody = h->HW + h->cond_len - 1;
-    if (h->Tbody > 256) { delete h; return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_create: context %d > 256", h->Tbody); }
+    if (h->Tbody > RQAMD_RQT_MAX_CONTEXT) {
+        const int tb = h->Tbody;
+        delete h;
+        return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_create: context %d > RQAMD_RQT_MAX_CONTEXT = %d", tb, RQAMD_RQT_MAX_CONTEXT);
+    }
+    if (h->Tbody > 256) {      // the chunked decode attention and the tiled prefill: head size 64, bf16 / fp16 cache (rqt_kernels.hip)
+        const int tb = h->Tbody;
+        if (h->kv_int8k) { delete h; return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_create: context %d > 256 with RQAMD_KV=%s (the 8-bit cache formats end at 256 tokens)", tb, getenv("RQAMD_KV")); }
+        if (c->embed_dim != c->n_head * 64) {
+            delete h;
+            return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_create: context %d > 256 needs head size 64 in the body stack (embed_dim=%d n_head=%d)", tb, c->embed_dim, c->n_head);
+        }
+    }
     const size_t E = h->E, V = h->V, Din = h->Din;
     const int vc = c->vocab_size_cond < 1 ? 1 : c->vocab_size_cond;
     const size_t per_layer = al(3 * E * E * 2) + al(E * E * 2) + 2 * al(4 * E * E * 2) + al(3 * E * 4) + al(4 * E * 4) + 6 * al(E * 4);
@@ -581,8 +594,10 @@ static int position_body(rqamd_rqt* h, const StepCtx& c, bool first_pos, int hos
         if (h->in_vq) RQ_TRY(embed_gemm(h, c, -1, 0, h->D, h->w_in, h->body_in_bias, -1, true, h->x, st));
         else RQ_TRY(tok_embed(h, c, -1, 0, h->D, h->pos_hw, true, -1, h->x, st));
     }
-    // a captured graph serves every position of the same 8-key bucket: bound t by the bucket's last position
-    return body_stack(h, B, h->st, h->cond_len - 1, ((host_pos + h->cond_len - 1) | 7), pend, st);
+    // a captured graph serves every position of the same 8-key bucket: bound t by the bucket's last position.  Beyond the last bucket
+    // (256 tokens and more) one launch sequence serves every later position: the chunked attention kernel's trip count follows the device counter
+    const int t_host = host_pos + h->cond_len - 1;
+    return body_stack(h, B, h->st, h->cond_len - 1, t_host >= 8 * (rqamd_rqt::NGRAPH - 1) ? h->Tbody - 1 : (t_host | 7), pend, st);
 }
 
 // head half: depth d of the position -- head stack, classifier, then the sampler / the teacher-forced copy / nothing
@@ -822,6 +837,7 @@ static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* co
     const bool want_cond = o.cond_logits || o.cond_logp;
     if (want_cond && (!h->w_ccls || h->n_ccls_seen < 4)) return rq_fail(RQAMD_ERR_STATE, "rqt: cond_classifier parameters not set");
     // chunk geometry
+    if (Tb > h->fwd_chunk_rows) return rq_fail(RQAMD_ERR_INVALID, "rqt one-pass forward: fwd.chunk_rows = %d holds no image (%d body tokens)", h->fwd_chunk_rows, Tb);
     int n_img = h->fwd_chunk_rows / Tb;            // images per body chunk
     if (n_img < 1) n_img = 1;
     if (n_img > B) n_img = B;

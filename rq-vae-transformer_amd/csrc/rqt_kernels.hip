@@ -678,6 +678,168 @@ static void launch_attn(const AttnDecodeArgs& a, int pairs_per_wave, hipStream_t
 }
 
 // =================================================================================================
+// Contexts beyond 256 keys (Tcap > 256: 32 x 32 code maps, long text prefixes; bf16 / fp16 cache, head size 64).  The kernels above hold every
+// K and V block of a pair in registers, which ends at 32 blocks; this one walks the context in register chunks of ATTN_LONG_CB blocks
+// (64 keys, 8 KB of K + 8 KB of V per wavefront) with an online softmax across chunks -- running max, running sum, rescaled accumulator --
+// and the loads of the next chunk issued before the arithmetic of the current one.  Lane map, append, arithmetic and the final
+// reduce-scatter are those of attn_run: lane (g, cc) owns chunk cc of key 8 * jj + g for K and V alike, bf16 q / k / v, fp32 dots, scale 1/8,
+// fp32 weights on bf16 values, one rounding of the output.  The trip count follows t (device counter), not Tcap: one captured graph with
+// t_max = Tcap - 1 serves every position.
+// NW = wavefronts per (row, head) pair.  1: a workgroup serves four heads of a row, as attn_decode_kernel does.  4: the four wavefronts of
+// a workgroup share ONE pair, wavefront w takes chunks w, w + 4, ..., and the partial (m, l, acc) meet in LDS -- for batches whose
+// rows * n_head wavefronts leave most of the chip idle while each walks ~1000 keys alone.  A wavefront without a chunk (contexts of fewer
+// than 4 chunks) contributes m = -inf, l = 0.
+#define ATTN_LONG_CB 8
+struct AttnLongChunk { rq_u128 k[ATTN_LONG_CB], v[ATTN_LONG_CB]; };
+
+// blocks c * CB .. of the pair's context: cache rows for keys j < t, this token's own k / v (from the qkv row: the cache row is written by
+// this launch) for j >= t -- clamped, the scores of j > t are masked
+static __device__ __forceinline__ void attn_long_load(AttnLongChunk& r, const bf16_t* kc, const bf16_t* vc, const bf16_t* qrow, int E, int c,
+                                                      int nblk, int t, int g, int cc) {
+#pragma unroll
+    for (int jj = 0; jj < ATTN_LONG_CB; ++jj) {
+        const int blk = c * ATTN_LONG_CB + jj;
+        if (blk >= nblk) continue;                                  // wave-uniform
+        const int j = blk * 8 + g;
+        const long off = (long)j * 64 + cc * 8;
+        r.k[jj] = ld128_kv(j >= t ? qrow + E + cc * 8 : kc + off);
+    }
+#pragma unroll
+    for (int jj = 0; jj < ATTN_LONG_CB; ++jj) {
+        const int blk = c * ATTN_LONG_CB + jj;
+        if (blk >= nblk) continue;
+        const int j = blk * 8 + g;
+        const long off = (long)j * 64 + cc * 8;
+        r.v[jj] = ld128_kv(j >= t ? qrow + 2 * E + cc * 8 : vc + off);
+    }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void attn_long_kernel(AttnDecodeArgs p) {
+    constexpr int CB = ATTN_LONG_CB;
+    __shared__ float s_part[4][66];                                 // NW == 4: per wavefront 64 un-normalised outputs, m, l
+    const int lane = threadIdx.x & 63;
+    const int wave = rq_uniform((int)(threadIdx.x >> 6));
+    const int h = NW == 1 ? (int)blockIdx.x * 4 + wave : (int)blockIdx.x;
+    const int w0 = NW == 1 ? 0 : wave;                              // first chunk of this wavefront
+    if (NW == 1 && h >= p.nh) return;                               // whole wavefront exits together
+    const int b = (int)blockIdx.y;
+    const int t = (p.step ? *p.step : 0) + p.step_off;
+    if (t < 0 || t >= p.Tcap || (p.t_max >= 0 && t > p.t_max)) rq_trap();      // host bound violated: never write past the cache
+    const int E = p.E;
+    const int cc = lane & 7, g = lane >> 3;
+    const int nblk = (t >> 3) + 1, nchunk = (nblk + CB - 1) / CB;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    const long pair = (long)b * p.nh + h;
+    const bf16_t* qrow = p.qkv + (long)b * 3 * E + h * 64;
+    bf16_t* kc = p.kc + pair * p.Tcap * 64;
+    bf16_t* vc = p.vc + pair * p.Tcap * 64;
+
+    const rq_u128 qv = ld128(qrow + cc * 8);
+    const rq_u128 kv_new = ld128(qrow + (lane < 8 ? E : 2 * E) + cc * 8);
+    AttnLongChunk nxt;
+    if (w0 < nchunk) attn_long_load(nxt, kc, vc, qrow, E, w0, nblk, t, g, cc);
+    if (NW == 1 || wave == 0) {                                     // append this token's k / v (read back by no wavefront of this launch)
+        if (lane < 8) st128_kv(kc + (long)t * 64 + cc * 8, kv_new);
+        else if (lane < 16) st128_kv(vc + (long)t * 64 + cc * 8, kv_new);
+    }
+    float qf[8], acc[8];
+    unpack8(qv, qf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    float m = NEG_INF, l = 0.f;                                     // m: uniform; l: this key group's share of the sum
+    for (int c = w0; c < nchunk; c += NW) {
+        const AttnLongChunk cur = nxt;
+        if (c + NW < nchunk) attn_long_load(nxt, kc, vc, qrow, E, c + NW, nblk, t, g, cc);
+        rq_sched_barrier();                                         // the next chunk's loads stay above this chunk's arithmetic
+        float sc[CB], cm = NEG_INF;
+#pragma unroll
+        for (int jj = 0; jj < CB; ++jj) {
+            float s = NEG_INF;
+            const int blk = c * CB + jj;
+            if (blk < nblk) {
+                float kf[8];
+                unpack8(cur.k[jj], kf);
+                float dot = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dot = fmaf(qf[e], kf[e], dot);
+                dot += rq_dpp_xor1(dot);
+                dot += rq_dpp_xor2(dot);
+                dot += rq_dpp_half_mirror(dot);
+                if (blk * 8 + g <= t) s = dot * 0.125f;             // 1/sqrt(64), attentions.py:87; causal mask :88-91
+            }
+            sc[jj] = s;
+            cm = fmaxf(cm, s);
+        }
+        cm = fmaxf(cm, rq_dpp_ror8(cm));                            // across the 8 key groups, as attn_run
+        cm = fmaxf(fmaxf(rq_readlane(cm, 0), rq_readlane(cm, 16)), fmaxf(rq_readlane(cm, 32), rq_readlane(cm, 48)));
+        const float mn = fmaxf(m, cm);                              // finite: key c * 64 of the chunk is <= t
+        const float alpha = (m == NEG_INF) ? 0.f : rq_fast_exp2((m - mn) * 1.4426950408889634f);
+        m = mn;
+        l *= alpha;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] *= alpha;
+#pragma unroll
+        for (int jj = 0; jj < CB; ++jj) {
+            if (c * CB + jj >= nblk) continue;
+            const float w = (sc[jj] == NEG_INF) ? 0.f : rq_fast_exp2((sc[jj] - mn) * 1.4426950408889634f);
+            l += w;
+            float vf[8];
+            unpack8(cur.v[jj], vf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(w, vf[e], acc[e]);
+        }
+    }
+    l += rq_dpp_ror8(l);                                            // over the key groups only: the 8 lanes of a group hold the same weights
+    l = (rq_readlane(l, 0) + rq_readlane(l, 16)) + (rq_readlane(l, 32) + rq_readlane(l, 48));
+    // reduce-scatter over the 8 key groups, as attn_run: every lane ends with one of the 64 outputs
+    const bool up32 = (lane & 32) != 0, up16 = (lane & 16) != 0, up8 = (lane & 8) != 0;
+    float a4[4], a2[2];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float keep = up32 ? acc[e + 4] : acc[e], send = up32 ? acc[e] : acc[e + 4];
+        a4[e] = keep + rq_shfl_xor(send, 32);
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const float keep = up16 ? a4[e + 2] : a4[e], send = up16 ? a4[e] : a4[e + 2];
+        a2[e] = keep + rq_shfl_xor(send, 16);
+    }
+    const float keep1 = up8 ? a2[1] : a2[0], send1 = up8 ? a2[0] : a2[1];
+    float o1 = keep1 + rq_dpp_ror8(send1);
+    const int eo = (up32 ? 4 : 0) + (up16 ? 2 : 0) + (up8 ? 1 : 0);
+    if constexpr (NW > 1) {
+        s_part[wave][lane] = o1;
+        if (lane == 0) { s_part[wave][64] = m; s_part[wave][65] = l; }
+        rq_syncthreads();
+        if (wave != 0) return;
+        float mm = NEG_INF;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) mm = fmaxf(mm, s_part[w][64]);
+        o1 = 0.f;
+        l = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = s_part[w][64];
+            const float f = (mw == NEG_INF) ? 0.f : rq_fast_exp2((mw - mm) * 1.4426950408889634f);
+            o1 = fmaf(f, s_part[w][lane], o1);
+            l = fmaf(f, s_part[w][65], l);
+        }
+    }
+    o1 *= 1.0f / l;
+    p.y[(long)b * E + h * 64 + cc * 8 + eo] = (bf16_t)(pack_bf16x2(o1, 0.f) & 0xffffu);
+}
+
+static int launch_attn_long(const AttnDecodeArgs& a, hipStream_t s) {
+    // few pairs: four wavefronts per pair (measured in profiles/long_context_bench.txt); RQAMD_ATTN_LONG_SPLIT=0 / 1 forces either form
+    const char* sp = getenv("RQAMD_ATTN_LONG_SPLIT");
+    const bool split = sp && *sp ? atoi(sp) != 0 : (long)a.rows * g_rq_row_scale * a.nh < 4096;
+    if (split) RQ_LAUNCH(attn_long_kernel<4>, dim3((unsigned)a.nh, (unsigned)a.rows), dim3(256), 0, s, a);
+    else RQ_LAUNCH(attn_long_kernel<1>, dim3((unsigned)((a.nh + 3) / 4), (unsigned)a.rows), dim3(256), 0, s, a);
+    return rq_check_launch("attn_long_kernel");
+}
+
+// =================================================================================================
 // Head sizes other than 64 (attentions.py:44-57 takes any embed_dim / n_head, and the two stacks carry their own n_head; every released
 // config has 64, which the kernels above are written for).  One wavefront per (row, head): q in LDS as fp32, lane = key for the scores
 // (fp32 dot products of bf16 operands, scale 1/sqrt(head_dim), attentions.py:87), a wavefront-wide softmax, then lane = output component
@@ -785,6 +947,20 @@ int rq_launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
         else if (a.ksc) RQ_LAUNCH(attn_small_kernel<true>, dim3((unsigned)((pairs + 31) / 32)), dim3(256), 0, s, a);
         else RQ_LAUNCH(attn_small_kernel<false>, dim3((unsigned)((pairs + 31) / 32)), dim3(256), 0, s, a);
         return rq_check_launch("attn_small_kernel");
+    }
+    // Contexts beyond 256 keys: the chunked kernel once the bound on t passes 255 (the catch-all graph of engine_rqt.hip has t_max = Tcap - 1);
+    // below that the register kernels, as at any other Tcap (the cache stride is an argument, not a template parameter).
+    // RQAMD_ATTN_LONG=1 (diagnostics, read at every launch): every context of more than 8 keys through the chunked kernel, at any Tcap.
+    const char* force_long = getenv("RQAMD_ATTN_LONG");
+    if ((force_long && atoi(force_long) != 0 && !a.ksc) || (a.Tcap > 256 && nj > 32)) {      // (the switch leaves the 8-bit caches alone)
+        if (a.ksc) return rq_fail(RQAMD_ERR_UNSUPPORTED, "attention: the 8-bit cache formats (RQAMD_KV) end at 256 keys (context %d)", a.Tcap);
+        return launch_attn_long(a, s);
+    }
+    if (a.Tcap > 256) {
+        if (a.ksc) return rq_fail(RQAMD_ERR_UNSUPPORTED, "attention: the 8-bit cache formats (RQAMD_KV) end at 256 keys (context %d)", a.Tcap);
+        if (nj <= 16) launch_attn<16, true>(a, 1, s);
+        else launch_attn<32, true>(a, 1, s);
+        return rq_check_launch("attn_decode_kernel");
     }
     if (a.Tcap <= 64) {
         switch (nj) {
@@ -911,6 +1087,88 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(AttnPrefillArgs p) {
     }
 }
 
+// The same for P > 255 (long text prefixes; the one-pass forward of a 32 x 32 map: P = 1087): one wavefront per (image, head, tile of 64
+// queries) instead of one per (image, head), K / V staged through LDS in key tiles of ATTN_TILE_KEYS keys (16 KB, whatever P is) instead of all
+// at once.  Lane = query, and the online softmax is carried across key tiles: every query sees keys 0 .. min(i0 + 63, P - 1) in order, through
+// the recurrence of attn_prefill_kernel -- the results are bit-identical to it.  Key tiles above the causal diagonal are never touched.
+// APPEND: the wavefront of query tile q writes cache rows q * 64 .. q * 64 + 63 (its diagonal key tile) -- every row exactly once.  bf16 / fp16
+// cache only (the 8-bit formats end at 256 keys and keep the kernel above).
+#define ATTN_TILE_KEYS 64
+template <bool APPEND>
+__global__ __launch_bounds__(64) void attn_prefill_tiled_kernel(AttnPrefillArgs p) {
+    constexpr int KT = ATTN_TILE_KEYS;
+    __shared__ rq_u128 sK[KT * 8], sV[KT * 8];                     // [key][8 chunks of 8 components]
+    const int lane = threadIdx.x;
+    const int P = p.P, E = p.E;
+    const int nqt = (P + 63) / 64;
+    const long blk = blockIdx.x;
+    const int qt = nqt - 1 - (int)(blk % nqt);                     // the longest tiles of a pair first
+    const long pair = blk / nqt;
+    const int img = (int)(pair / p.nh), hh = (int)(pair - (long)img * p.nh);
+    const bf16_t* q0 = p.qkv + (long)img * P * 3 * E + hh * 64;
+    const int i0 = qt * 64, i = i0 + lane;
+    const bool live = i < P;
+    const int iq = live ? i : P - 1;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    float qf[64], acc[64];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) unpack8(ld128(q0 + (long)iq * 3 * E + c * 8), qf + c * 8);
+#pragma unroll
+    for (int e = 0; e < 64; ++e) acc[e] = 0.f;
+    float m = NEG_INF, l = 0.f;
+    const int jend = i0 + 63 < P - 1 ? i0 + 63 : P - 1;           // wave-uniform; lanes mask keys j > i
+    for (int j0 = 0; j0 <= jend; j0 += KT) {
+        const int nk = jend + 1 - j0 < KT ? jend + 1 - j0 : KT;   // keys of this tile
+        rq_syncthreads();                                          // the previous tile has been read
+        for (int idx = lane; idx < nk * 8; idx += 64) {
+            const int j = j0 + (idx >> 3), c = idx & 7;
+            const rq_u128 kv = ld128(q0 + (long)j * 3 * E + E + c * 8), vv = ld128(q0 + (long)j * 3 * E + 2 * E + c * 8);
+            sK[idx] = kv;
+            sV[idx] = vv;
+            if (APPEND && j >= i0) {                               // the diagonal tile: these keys' cache rows
+                st128(p.kc + (pair * p.Tcap + j) * 64 + c * 8, kv);
+                st128(p.vc + (pair * p.Tcap + j) * 64 + c * 8, vv);
+            }
+        }
+        rq_syncthreads();
+        for (int jj = 0; jj < nk; ++jj) {
+            const int j = j0 + jj;
+            float dot = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float kf[8];
+                unpack8(sK[jj * 8 + c], kf);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dot = fmaf(qf[c * 8 + e], kf[e], dot);
+            }
+            const float sc = j <= iq ? dot * 0.125f : NEG_INF;    // 1/sqrt(64), attentions.py:87; causal mask :88-91
+            const float mn = fmaxf(m, sc);
+            const float alpha = (m == NEG_INF) ? 0.f : rq_fast_exp2((m - mn) * 1.4426950408889634f);
+            const float w = (sc == NEG_INF) ? 0.f : rq_fast_exp2((sc - mn) * 1.4426950408889634f);
+            l = l * alpha + w;
+            m = mn;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float vf[8];
+                unpack8(sV[jj * 8 + c], vf);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[c * 8 + e] = fmaf(w, vf[e], acc[c * 8 + e] * alpha);
+            }
+        }
+    }
+    if (live) {
+        const float inv = 1.0f / l;
+        bf16_t* o = p.y + ((long)img * P + i) * E + hh * 64;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            rq_u128 u;
+            u.x = pack_bf16x2(acc[c * 8 + 0] * inv, acc[c * 8 + 1] * inv); u.y = pack_bf16x2(acc[c * 8 + 2] * inv, acc[c * 8 + 3] * inv);
+            u.z = pack_bf16x2(acc[c * 8 + 4] * inv, acc[c * 8 + 5] * inv); u.w = pack_bf16x2(acc[c * 8 + 6] * inv, acc[c * 8 + 7] * inv);
+            st128(o + c * 8, u);
+        }
+    }
+}
+
 int rq_launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s) {
     const bool append = a.kc != nullptr;            // no cache: the one-pass teacher-forced forward
     if (!append && (a.vc || a.ksc || a.vsc)) return rq_fail(RQAMD_ERR_INVALID, "prefill attention: cache-free form with a cache pointer");
@@ -924,7 +1182,17 @@ int rq_launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s) {
         else RQ_LAUNCH(attn_generic_prefill_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, s, a);
         return rq_check_launch("attn_generic_prefill_kernel");
     }
-    if (a.nh < 1 || a.P < 1 || a.P > a.Tcap || a.P > 255) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %d tokens (cache %d, max 255)", a.P, a.Tcap);
+    if (a.nh < 1 || a.P < 1 || a.P > a.Tcap) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %d tokens (cache %d)", a.P, a.Tcap);
+    // P > 255: the tiled kernel.  RQAMD_PREFILL_TILED=1 (diagnostics, read at every launch): at any P (the 8-bit caches keep the kernel below).
+    const char* force_tiled = getenv("RQAMD_PREFILL_TILED");
+    if (a.P > 255 || (force_tiled && atoi(force_tiled) != 0 && !a.ksc)) {
+        if (a.ksc || a.vsc) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: the 8-bit cache formats (RQAMD_KV) end at 255 prefix tokens (%d)", a.P);
+        const long blocks = (long)a.n_img * a.nh * ((a.P + 63) / 64);
+        if (blocks > 0x7fffffffL) return rq_fail(RQAMD_ERR_UNSUPPORTED, "prefill attention: %ld (image, head, query tile) triples", blocks);
+        if (append) RQ_LAUNCH(attn_prefill_tiled_kernel<true>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+        else RQ_LAUNCH(attn_prefill_tiled_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, s, a);
+        return rq_check_launch("attn_prefill_tiled_kernel");
+    }
     const size_t smem = (size_t)a.P * 64 * 2 * 2;
     if (append) RQ_LAUNCH(attn_prefill_kernel<true>, dim3((unsigned)(a.n_img * a.nh)), dim3(64), smem, s, a);
     else RQ_LAUNCH(attn_prefill_kernel<false>, dim3((unsigned)(a.n_img * a.nh)), dim3(64), smem, s, a);

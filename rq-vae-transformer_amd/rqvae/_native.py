@@ -19,6 +19,7 @@ LIB16_PATH = os.path.join(_PKG, 'librqamd_f16.so')
 _lib = None
 _lib16 = None
 ABI_VERSION = 7
+RQT_MAX_CONTEXT = 1088      # include/rqamd.h: RQAMD_RQT_MAX_CONTEXT, the longest body context (H * W + block_size_cond - 1) rqamd_rqt_create accepts
 
 
 class RqamdError(RuntimeError):
