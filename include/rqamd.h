@@ -285,6 +285,12 @@ int rqamd_dbg_conv_out_bf16(const void* x, const float* w, const float* bias, co
  * = (ky, kx, ci, cout), y NHWC bf16 [B][H][W][128].  Needs H % 8 == 0, W % 32 == 0. */
 int rqamd_dbg_conv_in_bf16(const float* x, const float* w, const float* bias, int B, int H, int W, void* y, void* stream);
 
+/* One launch of the single-head spatial attention of AttnBlock (layers.py:158-182): qkv bf16 [B*T][3C] (q | k | v per token) ->
+ * out bf16 [B*T][C] = softmax(q k^T C^-0.5) v per image.  form: 0 the engine's own choice, 1 the wavefront-per-query kernel (T <= 1024),
+ * 2 the 64-token MFMA kernel (T == 64), 3 the tiled MFMA kernel (T % 64 == 0, 128 <= T <= 4096); forms 2 and 3 need C % 64 == 0,
+ * C <= 512.  A (form, shape) pair outside these limits returns RQAMD_ERR_UNSUPPORTED. */
+int rqamd_dbg_vae_attn(const void* qkv, int B, int T, int C, int form, void* out, void* stream);
+
 /* Kernel variants are selected by the number of rows (batch).  factor > 1 makes the selection logic see rows * factor, so
  * that the large-batch variants run on test-sized inputs (results must not change); 1 restores normal behaviour. */
 int rqamd_dbg_set_row_scale(int factor);

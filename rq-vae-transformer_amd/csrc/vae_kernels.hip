@@ -5,6 +5,7 @@
 // Reference call sites (rqvae/models/rqvae/):
 //   gn_stats / gn_apply  <- Normalize = GroupNorm(32, C, eps=1e-6) + nonlinearity = SiLU (layers.py:11-17)
 //   vae_attn_kernel      <- AttnBlock.forward (layers.py:158-182): softmax(q k^T * C^-0.5) v, single head
+//   (vae_attn_mfma_kernel at 64 tokens, vae_attn_tiled_kernel at 128 .. 4096 tokens: the same block on the matrix pipe)
 //   conv_in3_kernel      <- Encoder.conv_in (modules.py:23-27): 3 -> ch, reads the NCHW fp32 image
 //   conv_out3_kernel     <- Decoder.conv_out (modules.py:165-169): ch -> 3, writes the NCHW fp32 image
 //   repack_conv_kernel   <- nn.Conv2d weight (O,I,kh,kw) fp32 -> [O][kh][kw][I] bf16 (GEMM "W[N][K]")
@@ -323,23 +324,236 @@ __global__ __launch_bounds__(256) void vae_attn_mfma_kernel(const bf16_t* qkv, b
     }
 }
 
-int rq_launch_vae_attn(const bf16_t* qkv, bf16_t* out, int B, int T, int C, hipStream_t s) {
-    if (C % 8 != 0) return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: C %d", C);
+// The same attention for T = 128 .. 4096 tokens (16 x 16 to 64 x 64 maps), flash style: one workgroup of four wavefronts per (image,
+// 64-query tile) walks the image's keys in tiles of 64 and never holds more than one tile of scores.  Per key tile:
+//   1. S = Q K^T exactly as in vae_attn_mfma_kernel (operands from global memory in fragment layout; the tile's 64 Q rows are re-read
+//      per key tile and stay in the L1 / L2), fp32 scores * C^-0.5 into LDS; the V tile's staging loads are issued first;
+//   2. online softmax in fp32, 4 threads per query row, which keep the row's running max m and sum l in registers: alpha =
+//      exp(m_old - m_new) and l into LDS, p = exp(s - m_new) <= 1 UNNORMALISED into LDS as hi + lo of the 16-bit storage type
+//      (hi = round(p), lo = round(p - hi): 16 significant bits with bf16 -- a single bf16 P would add ~12 % to the kernel's mean
+//      error, which the one rounding of the output otherwise dominates);
+//   3. O^T = alpha O^T + V^T P_hi^T + V^T P_lo^T: wavefront w owns the 32-channel blocks w, w + 4, ... (CBW of them at most) for all
+//      64 queries, accumulators in registers over the whole key loop; in the D[channel][query] layout a lane holds ONE query per
+//      accumulator, so the rescale is one scalar per lane and accumulator.
+// After the last tile O^T / l is rounded once and stored (8-byte stores, as above).  LDS: V [64][C + 4], S [64][65] fp32, two P images
+// [64][72], alpha / l: 101.6 KB at C = 512 (Q and K never enter LDS), 52 KB at C = 128.  Two barriers per key tile: the one behind the
+// scores also ends the previous tile's reads of V and P.  Every
+// workgroup works on one image alone, in an order that depends on (T, C) only: image i of any batch equals its one-image launch.
+constexpr int VA_TILED_MAX_T = 4096;
+static inline size_t vae_attn_tiled_smem(int C) {
+    return (size_t)VA_T * (C + 4) * 2 + (size_t)VA_T * 65 * 4 + 2 * (size_t)VA_T * 72 * 2 + 2 * VA_T * 4;
+}
+template <int CBW>   // 32-channel blocks per wavefront: C <= 128 * CBW
+__global__ __launch_bounds__(256) void vae_attn_tiled_kernel(const bf16_t* qkv, bf16_t* out, int T, int C, float scale) {
+    RQ_DYN_SMEM(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = rq_uniform(tid >> 6);
+    const int l31 = lane & 31, kg = lane >> 5;
+    const int VP = C + 4;                                  // V row pitch (elements)
+    bf16_t* sV = (bf16_t*)smem;                            // [64][VP]
+    float* sS = (float*)(smem + (size_t)VA_T * VP * 2);    // [64][65]
+    bf16_t* sPh = (bf16_t*)(sS + VA_T * 65);               // [64][72] hi
+    bf16_t* sPl = sPh + VA_T * 72;                         // [64][72] lo
+    float* sA = (float*)(sPl + VA_T * 72);                 // [64] this tile's rescale factor per query
+    float* sL = sA + VA_T;                                 // [64] running sum per query
+    const int nqt = T >> 6;                                // query tiles = key tiles per image
+    const int img = blockIdx.x / nqt, q0 = (blockIdx.x % nqt) * VA_T;
+    const bf16_t* base = qkv + (long)img * T * 3 * C;
+    const int CC = C >> 3, n_chunk = VA_T * CC, nks = C >> 4, ncb = C >> 5;
+    const int mb = wave >> 1, nb = wave & 1;
+    const bf16_t* qp = base + (long)(q0 + mb * 32 + l31) * 3 * C + kg * 8;
+    const int srow = tid >> 2, spart = tid & 3;            // softmax: 4 threads per row, 16 keys each
+    float m_run = -__int_as_float(0x7f800000), l_run = 0.f;
+    f32x16 acc[CBW][2];
+#pragma unroll
+    for (int ci = 0; ci < CBW; ++ci)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ci][qb][r] = 0.f;
+
+    for (int kt = 0; kt < nqt; ++kt) {
+        const bf16_t* kbase = base + (long)kt * VA_T * 3 * C;
+        // ---- V tile: staging loads (C / 32 <= 4 CBW chunks per thread), stored to LDS behind the scores
+        rq_u128 vr[4 * CBW];
+#pragma unroll
+        for (int i = 0; i < 4 * CBW; ++i) {
+            const int id = tid + 256 * i;
+            if (id < n_chunk) vr[i] = ld128(kbase + (long)(id / CC) * 3 * C + 2 * C + (id % CC) * 8);
+        }
+        // ---- 1. scores of this wavefront's 32 x 32 block
+        {
+            const bf16_t* kp = kbase + (long)(nb * 32 + l31) * 3 * C + C + kg * 8;
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            for (int k0 = 0; k0 < nks; k0 += 4) {
+                rq_u128 a[4], b[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    a[j] = zero128(); b[j] = zero128();
+                    if (k0 + j < nks) { a[j] = ld128(qp + (k0 + j) * 16); b[j] = ld128(kp + (k0 + j) * 16); }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k0 + j < nks) s = rq_mfma_32x32x16_bf16(as_bf16x8(a[j]), as_bf16x8(b[j]), s);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sS[(mb * 32 + (r >> 2) * 8 + kg * 4 + (r & 3)) * 65 + nb * 32 + l31] = s[r] * scale;
+        }
+        rq_syncthreads();                                  // every wavefront is done with the previous tile's V and P
+#pragma unroll
+        for (int i = 0; i < 4 * CBW; ++i) {
+            const int id = tid + 256 * i;
+            if (id < n_chunk) {
+                uint64_t* d = (uint64_t*)(sV + (id / CC) * VP + (id % CC) * 8);
+                d[0] = (uint64_t)vr[i].x | ((uint64_t)vr[i].y << 32);
+                d[1] = (uint64_t)vr[i].z | ((uint64_t)vr[i].w << 32);
+            }
+        }
+        // ---- 2. online softmax
+        {
+            float v[16], mx = -__int_as_float(0x7f800000);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { v[i] = sS[srow * 65 + spart * 16 + i]; mx = fmaxf(mx, v[i]); }
+            mx = fmaxf(mx, rq_shfl_xor(mx, 1));
+            mx = fmaxf(mx, rq_shfl_xor(mx, 2));
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = expf(m_run - m_new);       // first tile: exp(-inf) = 0 on accumulators that are 0
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { v[i] = expf(v[i] - m_new); sum += v[i]; }
+            sum += rq_shfl_xor(sum, 1);
+            sum += rq_shfl_xor(sum, 2);
+            l_run = fmaf(l_run, alpha, sum);
+            m_run = m_new;
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) {
+                const uint32_t hi = pack_bf16x2(v[i], v[i + 1]);
+                float h0, h1;
+                rq_unpack2(hi, h0, h1);
+                *(uint32_t*)(sPh + srow * 72 + spart * 16 + i) = hi;
+                *(uint32_t*)(sPl + srow * 72 + spart * 16 + i) = pack_bf16x2(v[i] - h0, v[i + 1] - h1);
+            }
+            if (spart == 0) { sA[srow] = alpha; sL[srow] = l_run; }
+        }
+        rq_syncthreads();
+        // ---- 3. O^T = alpha O^T + V^T P^T
+        {
+            float al[2];
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) al[qb] = sA[qb * 32 + l31];
+#pragma unroll
+            for (int ci = 0; ci < CBW; ++ci)
+                if (wave + 4 * ci < ncb) {
+#pragma unroll
+                    for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[ci][qb][r] *= al[qb];
+                }
+#pragma unroll 1                                        // (unrolled, the 2-byte V reads of all four steps are hoisted: 128 VGPRs at C = 512)
+            for (int ks = 0; ks < 4; ++ks) {
+                rq_u128 ph[2], pl[2];                      // B operands: P[q = qb*32 + l31][ks*16 + kg*8 ..]
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb) {
+                    ph[qb] = ld128(sPh + (qb * 32 + l31) * 72 + ks * 16 + kg * 8);
+                    pl[qb] = ld128(sPl + (qb * 32 + l31) * 72 + ks * 16 + kg * 8);
+                }
+#pragma unroll
+                for (int ci = 0; ci < CBW; ++ci) {
+                    const int cb = wave + 4 * ci;
+                    if (cb < ncb) {
+                        const bf16_t* vcol = sV + cb * 32 + l31;
+                        uint32_t w4[4];
+#pragma unroll
+                        for (int e = 0; e < 8; e += 2) {
+                            const uint32_t lo = vcol[(ks * 16 + kg * 8 + e) * VP], hi = vcol[(ks * 16 + kg * 8 + e + 1) * VP];
+                            w4[e >> 1] = lo | (hi << 16);
+                        }
+                        rq_u128 af;
+                        af.x = w4[0]; af.y = w4[1]; af.z = w4[2]; af.w = w4[3];
+#pragma unroll
+                        for (int qb = 0; qb < 2; ++qb) {
+                            acc[ci][qb] = rq_mfma_32x32x16_bf16(as_bf16x8(af), as_bf16x8(ph[qb]), acc[ci][qb]);
+                            acc[ci][qb] = rq_mfma_32x32x16_bf16(as_bf16x8(af), as_bf16x8(pl[qb]), acc[ci][qb]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // ---- O^T / l, one rounding (sL of the last tile was written before that tile's second barrier)
+    float inv[2];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) inv[qb] = 1.0f / sL[qb * 32 + l31];
+#pragma unroll
+    for (int ci = 0; ci < CBW; ++ci) {
+        const int cb = wave + 4 * ci;
+        if (cb < ncb) {
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                bf16_t* o = out + ((long)img * T + q0 + qb * 32 + l31) * C + cb * 32 + kg * 4;
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq)
+                    *(uint64_t*)(o + rq * 8) = (uint64_t)pack_bf16x2(acc[ci][qb][rq * 4] * inv[qb], acc[ci][qb][rq * 4 + 1] * inv[qb]) |
+                                               ((uint64_t)pack_bf16x2(acc[ci][qb][rq * 4 + 2] * inv[qb], acc[ci][qb][rq * 4 + 3] * inv[qb]) << 32);
+            }
+        }
+    }
+}
+
+template <int CBW>
+static int vae_attn_tiled_launch(const bf16_t* qkv, bf16_t* out, int B, int T, int C, float scale, hipStream_t s) {
+    static RqDeviceOnce attr_once;
+    if (attr_once.first()) (void)hipFuncSetAttribute((const void*)vae_attn_tiled_kernel<CBW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    RQ_LAUNCH(vae_attn_tiled_kernel<CBW>, dim3((unsigned)((long)B * (T / VA_T))), dim3(256), vae_attn_tiled_smem(C), s, qkv, out, T, C, scale);
+    return rq_check_launch("vae_attn_tiled_kernel");
+}
+
+// form: 0 the routing of the engine, 1 vae_attn_kernel, 2 vae_attn_mfma_kernel, 3 vae_attn_tiled_kernel
+static int vae_attn_launch(const bf16_t* qkv, bf16_t* out, int B, int T, int C, int form, hipStream_t s) {
+    if (B < 1 || T < 1 || C < 8 || C % 8 != 0) return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: B %d, T %d, C %d", B, T, C);
     const float scale = 1.0f / sqrtf((float)C);      // int(c)**(-0.5), layers.py:170
-    static const bool no_mfma = getenv("RQAMD_VAE_ATTN_VALU") != nullptr;      // A/B switch
-    if (T == VA_T && C % 64 == 0 && C <= 512 && !no_mfma) {
+    static const bool no_mfma = getenv("RQAMD_VAE_ATTN_VALU") != nullptr;      // A/B switch: the wavefront-per-query kernel wherever it runs
+    const bool c_ok = C % 64 == 0 && C <= 512;
+    const bool mfma_ok = T == VA_T && c_ok;
+    const bool tiled_ok = T % VA_T == 0 && T >= 2 * VA_T && T <= VA_TILED_MAX_T && c_ok;
+    if (form == 0) form = (mfma_ok && !no_mfma) ? 2 : (tiled_ok && !(no_mfma && T <= 1024)) ? 3 : 1;
+    if (form == 2) {
+        if (!mfma_ok) return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: the 64-token MFMA kernel needs T == 64 and C %% 64 == 0, C <= 512 (T %d, C %d)", T, C);
         const size_t smem = (size_t)VA_T * (C + 4) * 2 + (size_t)VA_T * 65 * 4 + (size_t)VA_T * 72 * 2;
         static RqDeviceOnce attr_once;
         if (attr_once.first()) (void)hipFuncSetAttribute((const void*)vae_attn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         RQ_LAUNCH(vae_attn_mfma_kernel, dim3((unsigned)B), dim3(256), smem, s, qkv, out, C, scale);
         return rq_check_launch("vae_attn_mfma_kernel");
     }
+    if (form == 3) {
+        if (!tiled_ok)
+            return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: the tiled kernel needs T %% 64 == 0, 128 <= T <= %d and C %% 64 == 0, C <= 512 (T %d, C %d)",
+                           VA_TILED_MAX_T, T, C);
+        const int cbw = (C / 32 + 3) / 4;
+        return cbw == 1 ? vae_attn_tiled_launch<1>(qkv, out, B, T, C, scale, s) : cbw == 2 ? vae_attn_tiled_launch<2>(qkv, out, B, T, C, scale, s)
+             : cbw == 3 ? vae_attn_tiled_launch<3>(qkv, out, B, T, C, scale, s) : vae_attn_tiled_launch<4>(qkv, out, B, T, C, scale, s);
+    }
+    if (form != 1) return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: unknown kernel form %d", form);
+    if (T > VA_TILED_MAX_T) return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: %d tokens > %d", T, VA_TILED_MAX_T);
+    if (T > 1024)
+        return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: %d tokens > 1024 need T %% 64 == 0 and C %% 64 == 0, C <= 512 (C %d); at most %d tokens then",
+                       T, C, VA_TILED_MAX_T);
     dim3 grid((unsigned)(((long)B * T + 3) / 4));
     if (T <= 64) RQ_LAUNCH(vae_attn_kernel<1>, grid, dim3(256), 0, s, qkv, out, B, T, C, scale);
     else if (T <= 256) RQ_LAUNCH(vae_attn_kernel<4>, grid, dim3(256), 0, s, qkv, out, B, T, C, scale);
-    else if (T <= 1024) RQ_LAUNCH(vae_attn_kernel<16>, grid, dim3(256), 0, s, qkv, out, B, T, C, scale);
-    else return rq_fail(RQAMD_ERR_UNSUPPORTED, "vae attention: %d tokens > 1024", T);
+    else RQ_LAUNCH(vae_attn_kernel<16>, grid, dim3(256), 0, s, qkv, out, B, T, C, scale);
     return rq_check_launch("vae_attn_kernel");
+}
+
+int rq_launch_vae_attn(const bf16_t* qkv, bf16_t* out, int B, int T, int C, hipStream_t s) {
+    return vae_attn_launch(qkv, out, B, T, C, 0, s);
+}
+
+extern "C" int rqamd_dbg_vae_attn(const void* qkv, int B, int T, int C, int form, void* out, void* stream) {
+    if (!qkv || !out) return rq_fail(RQAMD_ERR_INVALID, "dbg_vae_attn: null argument");
+    if (form < 0 || form > 3) return rq_fail(RQAMD_ERR_INVALID, "dbg_vae_attn: form %d (0 .. 3)", form);
+    return vae_attn_launch((const bf16_t*)qkv, (bf16_t*)out, B, T, C, form, (hipStream_t)stream);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -100,6 +100,7 @@ _SIGS = {
     'rqamd_dbg_ups_subpixel_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_dbg_conv_out_bf16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_vae_attn': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -437,6 +438,20 @@ def dbg_conv_out(x, w, bias, gn=None):
     check(lib().rqamd_dbg_conv_out_bf16(ptr(x, torch.bfloat16), ptr(w, torch.float32), ptr(bias, torch.float32), ptr(gn),
                                         B, H, W, Cin, Cout, ptr(y), stream_of(x)))
     return y
+
+
+def dbg_vae_attn(qkv, form=0, out=None):
+    """diagnostics: AttnBlock's attention alone; qkv (B, T, 3C) bf16 -> (B, T, C) bf16 = softmax(q k^T C^-0.5) v per image.  form 0: the
+    engine's choice, 1 the wavefront-per-query kernel, 2 the 64-token MFMA kernel, 3 the tiled MFMA kernel (NotImplementedError for a
+    shape the form does not serve)."""
+    B, T, C3 = qkv.shape
+    if C3 % 3 != 0:
+        raise ValueError(f'qkv of shape {tuple(qkv.shape)}: last dimension is not 3 C')
+    if out is None:
+        out = torch.empty((B, T, C3 // 3), dtype=torch.bfloat16, device=qkv.device)
+    with on_device_of(qkv):
+        check(lib().rqamd_dbg_vae_attn(ptr(qkv, torch.bfloat16), B, T, C3 // 3, int(form), ptr(out, torch.bfloat16), stream_of(qkv)))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- engines
