@@ -190,6 +190,20 @@ int rqamd_rqt_sample(rqamd_rqt* h, const int64_t* partial, const int64_t* cond, 
                      const float* const* codebooks, int start_h, int start_w, float temperature,
                      const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
                      int use_graph, int64_t* codes_out, void* stream);
+/* Masked form of rqamd_rqt_sample (inpainting, outpainting, depth refinement, a region per image); additive, ABI v7.
+ * keep (batch,H,W,D) bytes on the DEVICE, nonzero = the code is kept: it stays as `partial` gives it and everything drawn later is
+ * conditioned on it.  Every other code is drawn as rqamd_rqt_sample draws it (same logits, filter and Philox counter
+ * offset + pos * D + d of its row); its value in `partial` is never read.  With the seed and offset of an unmasked call and kept
+ * codes equal to what that call drew, the result is that call's, bit for bit.  `keep` is copied into the handle when the call
+ * starts: the caller may free it once the stream has reached that point, and captured graphs never hold it.
+ * pos_active_host: H * W bytes on the HOST or NULL (every position active).  0 at position p is the caller's promise that
+ * every code of p is kept in every row: p then runs the body stack only, as the positions before start_h / start_w do, and
+ * nothing runs after the last active position.  There is no start_h / start_w: a kept prefix is part of `keep`.
+ * Masked calls replay captured graphs of their own: alternating with rqamd_rqt_sample recaptures nothing. */
+int rqamd_rqt_sample_masked(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                            const int64_t* cond, int batch, const float* const* codebooks, float temperature,
+                            const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
+                            int use_graph, int64_t* codes_out, void* stream);
 /* rqamd_rqt_logits <- the same cached_forward stepping (transformers.py:190-287) driven
  * teacher-forced over given codes, returning every step's logits: logits_out (batch,H,W,D,vocab) fp32.
  * This is the parity hook against RQTransformer.forward (transformers.py:113-188). */

@@ -82,6 +82,7 @@ struct rqamd_rqt {
     int* st;            // [0] = spatial position
     uint64_t* rng;      // {seed, offset}
     int* smp_redo;      // [rows] sampler workspace (rows the top-k kernel hands back to the general kernel)
+    uint8_t* keep;      // [rows][HW][D] keep flags of a masked sampling call (rqamd_rqt_sample_masked), laid out like xs
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -90,8 +91,10 @@ struct rqamd_rqt {
     // graph cache
     // one captured position per 8-key bucket of the body context (the attention kernel variant is baked in); the last one is the catch-all of
     // contexts beyond 256 tokens: captured once with t_max = Tbody - 1, it serves every position from token 256 on (position_body)
+    // two sets: [0] unmasked sampling, [1] masked sampling (the sampler launches carry the keep-flag pointer, a kernel argument).
+    // Both are captured under the same key, so a caller that alternates between the two forms replays what it captured before
     static constexpr int NGRAPH = 33;
-    hipGraphExec_t gexec[NGRAPH] = {};
+    hipGraphExec_t gexec[2][NGRAPH] = {};
     struct Key { int B; float T; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey;
     bool gvalid = false;
 
@@ -230,7 +233,7 @@ extern "C" int rqamd_rqt_create(const rqamd_rqt_config* c, rqamd_rqt** out) {
 
 extern "C" int rqamd_rqt_destroy(rqamd_rqt* h) {
     if (!h) return RQAMD_OK;
-    for (auto& g : h->gexec) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& set : h->gexec) for (auto& g : set) if (g) (void)hipGraphExecDestroy(g);
     for (auto e : h->prof.ev) (void)hipEventDestroy(e);
     for (auto e : h->prof.ev_attn) (void)hipEventDestroy(e);
     delete h;
@@ -388,7 +391,8 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     const size_t prow = (size_t)prefill_chunk(h, B) * (h->cond_len - 1);
     const size_t rows = brows > prow ? brows : prow;              // activation rows (decode step or prefill chunk)
     size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + al(brows * V * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
-                   + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4);
+                   + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4)
+                   + al(brows * h->HW * h->D);
     RQ_TRY(h->ws.reserve(total));
     char* p = (char*)h->ws.p;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
@@ -400,6 +404,7 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     h->ain = (bf16_t*)take(brows * h->Din * 2);
     h->xs = (int64_t*)take(brows * h->HW * h->D * 8); h->cond = (int64_t*)take(brows * h->cond_len * 8);
     h->st = (int*)take(64); h->rng = (uint64_t*)take(64); h->smp_redo = (int*)take(brows * 4);
+    h->keep = (uint8_t*)take(brows * h->HW * h->D);
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
     const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
     // (8-bit keys: half the bytes for K plus one fp32 scale per (row, head, position))
@@ -548,6 +553,7 @@ struct StepCtx {
     const int* top_k;
     const float* top_p;
     bool sample;           // run the sampler (else teacher-forced)
+    const uint8_t* keep;   // sampling: per-code keep flags (h->keep) of a masked call, or null
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -638,6 +644,7 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
         SampleArgs s{};
         s.logits = h->logits; s.rows = B; s.V = h->V; s.temperature = c.temperature; s.top_k = c.top_k[d]; s.top_p = c.top_p[d];
         s.redo = h->smp_redo; s.rng = h->rng; s.pos = h->st; s.d = d; s.D = h->D; s.out = h->xs; s.out_stride = (long)h->HW * h->D;
+        s.keep = c.keep; s.keep_stride = s.out_stride;
         RQ_TRY(rq_launch_sample(s, st));
     } else if (c.logits_out) {
         float* dst = c.logits_out + ((long)host_pos * h->D + d) * h->V;
@@ -693,21 +700,32 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
     return RQAMD_OK;
 }
 
-static int run_all(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const int64_t* cond, int start_idx, bool use_graph,
-                   int64_t* codes_out, hipStream_t st) {
+// `keep` / `pos_active` (masked sampling): device flags per code, copied into h->keep before anything reads them, and the host's
+// per-position activity (null: every position).  An inactive position has every code given in every row: body stack only, like the
+// positions before start_idx.  Nothing runs after the last active position -- nobody reads its KV entries.
+static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, const int64_t* cond, int start_idx, bool use_graph,
+                   int64_t* codes_out, hipStream_t st, const uint8_t* keep = nullptr, const uint8_t* pos_active = nullptr) {
+    StepCtx c = c_in;
     const int B = c.B;
     RQ_TRY(begin_batch(h, c, partial, cond, st));
-    for (int pos = 0; pos < h->HW; ++pos) {
-        const bool do_head = pos >= start_idx;
+    int n_pos = h->HW;
+    if (keep) {
+        RQ_HIP(hipMemcpyAsync(h->keep, keep, (size_t)B * h->HW * h->D, hipMemcpyDeviceToDevice, st));
+        c.keep = h->keep;
+        while (pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
+    }
+    hipGraphExec_t* gexec = h->gexec[keep ? 1 : 0];
+    for (int pos = 0; pos < n_pos; ++pos) {
+        const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
         const bool graphable = use_graph && c.sample && do_head && pos >= 1 && !h->prof.on;
         if (graphable) {
             if (!h->gvalid) {
-                for (auto& g : h->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+                for (auto& set : h->gexec) for (auto& g : set) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
                 h->gvalid = true;
             }
             int bucket = (pos + h->cond_len - 1) >> 3;
             if (bucket >= rqamd_rqt::NGRAPH) bucket = rqamd_rqt::NGRAPH - 1;
-            if (!h->gexec[bucket]) {
+            if (!gexec[bucket]) {
                 hipGraph_t g = nullptr;
                 hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
                 if (e == hipSuccess) {
@@ -716,7 +734,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const
                     hipError_t e2 = hipStreamEndCapture(st, &g);
                     if (rc != RQAMD_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
                     if (e2 != hipSuccess) return rq_fail(RQAMD_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e2));
-                    e2 = hipGraphInstantiate(&h->gexec[bucket], g, nullptr, nullptr, 0);
+                    e2 = hipGraphInstantiate(&gexec[bucket], g, nullptr, nullptr, 0);
                     (void)hipGraphDestroy(g);
                     if (e2 != hipSuccess) return rq_fail(RQAMD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
                 } else {
@@ -728,8 +746,8 @@ static int run_all(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const
                     use_graph = false;
                 }
             }
-            if (h->gexec[bucket]) {
-                RQ_HIP(hipGraphLaunch(h->gexec[bucket], st));
+            if (gexec[bucket]) {
+                RQ_HIP(hipGraphLaunch(gexec[bucket], st));
                 continue;
             }
         }
@@ -740,28 +758,23 @@ static int run_all(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const
     return RQAMD_OK;
 }
 
-extern "C" int rqamd_rqt_sample(rqamd_rqt* h, const int64_t* partial, const int64_t* cond, int batch,
-                                const float* const* codebooks, int start_h, int start_w, float temperature,
-                                const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
-                                int use_graph, int64_t* codes_out, void* stream) {
-    if (!h || !partial || !codebooks || !top_k || !top_p || !codes_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: null argument");
-    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: batch < 1");
-    if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: temperature must be > 0");
+// rqamd_rqt_sample / rqamd_rqt_sample_masked behind their argument checks
+static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active, const int64_t* cond, int batch,
+                       const float* const* codebooks, int start_idx, float temperature, const int* top_k, const float* top_p,
+                       uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     h->step_on = false;
     RQ_TRY(ensure_batch(h, batch));
     StepCtx c{};
     c.B = batch; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
-    // graph cache key: anything baked into kernel arguments
+    // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their own)
     rqamd_rqt::Key k{};
     k.B = batch; k.T = temperature; k.stream = stream;
     for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; k.cb[d] = codebooks[d]; }
     if (!h->gvalid || memcmp(&k, &h->gkey, sizeof(k)) != 0) { h->gvalid = false; h->gkey = k; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
-    int start_idx = start_h * h->cfg.W + start_w;
-    if (start_idx < 0) start_idx = 0;
-    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st));
+    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st, keep, pos_active));
     if (h->prof.on) {
         RQ_HIP(hipStreamSynchronize(st));
         double ms = 0;
@@ -782,6 +795,35 @@ extern "C" int rqamd_rqt_sample(rqamd_rqt* h, const int64_t* partial, const int6
         h->prof.attn_launches = (int64_t)(h->prof.used_attn / 2);
     }
     return RQAMD_OK;
+}
+
+extern "C" int rqamd_rqt_sample(rqamd_rqt* h, const int64_t* partial, const int64_t* cond, int batch,
+                                const float* const* codebooks, int start_h, int start_w, float temperature,
+                                const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
+                                int use_graph, int64_t* codes_out, void* stream) {
+    if (!h || !partial || !codebooks || !top_k || !top_p || !codes_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: null argument");
+    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: batch < 1");
+    if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: temperature must be > 0");
+    int start_idx = start_h * h->cfg.W + start_w;
+    if (start_idx < 0) start_idx = 0;
+    return sample_impl(h, partial, nullptr, nullptr, cond, batch, codebooks, start_idx, temperature, top_k, top_p, seed, offset, use_graph,
+                       codes_out, stream);
+}
+
+// Masked form (include/rqamd.h): a kept code stays as `partial` gives it, every other code is drawn exactly as rqamd_rqt_sample draws
+// it -- same logits, same filter, same Philox counter offset + pos * D + d of its row -- so a masked call whose kept codes are what
+// the unmasked call drew reproduces that call bit for bit.  The sampler kernels skip kept (row, slot)s; everything else is the
+// unmasked launch sequence.
+extern "C" int rqamd_rqt_sample_masked(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                                       const int64_t* cond, int batch, const float* const* codebooks, float temperature,
+                                       const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
+                                       int use_graph, int64_t* codes_out, void* stream) {
+    if (!h || !partial || !keep || !codebooks || !top_k || !top_p || !codes_out)
+        return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: null argument");
+    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: batch < 1");
+    if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: temperature must be > 0");
+    return sample_impl(h, partial, keep, pos_active_host, cond, batch, codebooks, 0, temperature, top_k, top_p, seed, offset, use_graph,
+                       codes_out, stream);
 }
 
 extern "C" int rqamd_rqt_logits(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,

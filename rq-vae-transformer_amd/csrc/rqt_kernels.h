@@ -85,6 +85,8 @@ struct SampleArgs {
     long out_stride;
     float* probs_out;       // [rows][V] filtered distribution, or null
     int* redo;              // [rows] workspace: rows the top-k kernel hands to the general kernel (null: general kernel only)
+    const uint8_t* keep;    // keep[row * keep_stride + (*pos * D + d)] != 0: the code is given -- no draw, `out` and `redo` untouched (null: draw every row)
+    long keep_stride;
 };
 
 int rq_launch_resid_ln(const ResidLnArgs& a, hipStream_t s);

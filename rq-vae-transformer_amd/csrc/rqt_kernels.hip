@@ -1436,6 +1436,13 @@ static __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, u
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// keep flags of masked sampling (rqamd_rqt_sample_masked): a (row, slot) whose code is given is left alone.  The test is the first
+// thing a workgroup does, before `redo` is read or written: a stale redo[row] of an earlier step must not hand a kept code to the
+// general kernel's second pass.  Uniform over the workgroup (one byte, the same address for every thread).
+static __device__ __forceinline__ bool sample_kept(const SampleArgs& p, int row) {
+    return p.keep && p.keep[(long)row * p.keep_stride + (p.pos ? (*p.pos) * p.D + p.d : 0)] != 0;
+}
+
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1445,6 +1452,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     unsigned* hist = (unsigned*)(redi + 16);   // [256]
     unsigned* bcast = hist + 256;              // [4]
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
+    if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (p.redo && !p.redo[row]) return;        // second pass after sample_topk_kernel: only the rows it handed back
     const float* lg = p.logits + (long)row * V;
     const float NEG_INF = -__int_as_float(0x7f800000);
@@ -1782,6 +1790,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
+    if (sample_kept(p, row)) return;           // masked sampling: the code is given (redo[row] is neither written nor read)
     const float* lg = p.logits + (long)row * V;
     const int V4 = V >> 2;
     // thread t owns float4 groups t, t+256, ...: value 4j+e is vocabulary index (t + 256 j) * 4 + e
@@ -1900,6 +1909,7 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
+    if (sample_kept(p, row)) return;           // masked sampling: the code is given
     const float* lg = p.logits + (long)row * V;
     const float inv_t = 1.0f / p.temperature;
     const int slot = p.pos ? (*p.pos) * p.D + p.d : 0;

@@ -75,6 +75,9 @@ _SIGS = {
     'rqamd_rqt_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int,
                                    C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int,
                                    C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_masked': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+                                          C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward_onepass': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -599,6 +602,32 @@ class RqtEngine(_Engine):
                                                  int(start_loc[0]), int(start_loc[1]), float(temperature), tk, tp,
                                                  int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(bool(use_graph)),
                                                  ptr(out), stream_of(partial)))
+        return out
+
+    def sample_masked(self, partial, keep, pos_active, cond, codebooks, temperature, top_k, top_p, seed, offset, use_graph):
+        """rqamd_rqt_sample_masked: `keep` (B,H,W,D) uint8 on the engine's device, nonzero = the code of `partial` is kept; `pos_active`
+        a host sequence of H * W flags (0: every code of the position is kept in every row -- the caller's promise) or None."""
+        self._check(partial, cond, codebooks)
+        if keep is None:
+            kp = None                                    # (the library refuses it: RQAMD_ERR_INVALID)
+        else:
+            if keep.dtype != torch.uint8 or tuple(keep.shape) != tuple(partial.shape):
+                raise ValueError(f'keep of shape {tuple(keep.shape)} / {keep.dtype}; expected {tuple(partial.shape)} / torch.uint8')
+            self._on_my_device(keep)
+            kp = ptr(keep, torch.uint8)
+        B = partial.shape[0]
+        c = self.cfg
+        pa = None
+        if pos_active is not None:
+            if len(pos_active) != c.H * c.W:
+                raise ValueError(f'pos_active has {len(pos_active)} entries; expected {c.H * c.W}')
+            pa = (C.c_uint8 * (c.H * c.W))(*[1 if a else 0 for a in pos_active])
+        out = torch.empty_like(partial)
+        D = c.D
+        cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
+        self._run(lambda: self._L.rqamd_rqt_sample_masked(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), B, cbs,
+                                                        float(temperature), tk, tp, int(seed) & (2 ** 64 - 1),
+                                                        int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
         return out
 
     def logits(self, codes, cond, codebooks):

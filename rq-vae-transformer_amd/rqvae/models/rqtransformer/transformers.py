@@ -296,8 +296,13 @@ class RQTransformer(Stage2Model):
 
     @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
-               amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True):
-        """transformers.py:294-369"""
+               amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, keep_mask=None):
+        """transformers.py:294-369.  ``keep_mask`` (not in the reference; keyword-only): codes of `partial_sample` to hold fixed --
+        (B,H,W,D), (B,H,W), (H,W,D) or (H,W), bool or integer (nonzero = kept); a mask without D applies to every depth, one without B
+        to every image.  A kept code stays as given and conditions everything drawn after it; every other code is drawn exactly as
+        the unmasked call draws it (same logits, filter and Philox counter), whatever `partial_sample` holds there.  Positions before
+        `start_loc` are kept in addition.  Inpainting, outpainting, depth refinement and a region per image are masks; None: the
+        reference's behaviour."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
@@ -323,18 +328,60 @@ class RQTransformer(Stage2Model):
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
         c = self._cond(cond, B, device)
+        keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
+        if keep is not None and (self.sampler == 'torch' or not cached):
+            # the host loops run teacher-forced passes over the whole map, which embed every code: what `partial_sample` holds at a
+            # code to be drawn is never used, but it has to be a code (the engine's masked entry point never reads it)
+            xs = torch.where(keep, xs, torch.zeros_like(xs))
         if self.sampler == 'torch':
             if not cached:
                 raise NotImplementedError("sampler='torch' steps the cached engine; cached=False is available with the default sampler")
-            return self._sample_torch_multinomial(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list)
+            return self._sample_torch_multinomial(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, keep, active)
         seed, offset = self._draw_rng(device, H * W * D)
         if not cached:
-            return self._sample_uncached(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset)
+            return self._sample_uncached(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active)
+        if keep is not None:
+            keep8 = keep.to(torch.uint8).contiguous()
+            pos_active = [bool(a) for a in active.any(dim=1).tolist()]
+            return self._on_side_stream(device, lambda: eng.sample_masked(xs, keep8, pos_active, c, cbs, temperature, top_k_list,
+                                                                          top_p_list, seed, offset, self.use_graph))
         out = self._on_side_stream(device, lambda: eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list,
                                                               seed, offset, self.use_graph))
         return out
 
-    def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset):
+    def _keep_flags(self, keep_mask, xs, start_loc):
+        """keep_mask of sample() -> (keep (B,H,W,D) bool on the device of `xs`, active (H*W, D) bool on the host: some row draws that
+        code).  One device-to-host transfer carries both the activity and the range check of the kept codes: the engine embeds them,
+        and its gather kernels trap on a code outside the vocabulary.  Codes that are not kept are not looked at."""
+        (B, H, W, D) = xs.shape
+        if not torch.is_tensor(keep_mask):
+            keep_mask = torch.as_tensor(keep_mask)
+        if keep_mask.dtype.is_floating_point or keep_mask.dtype.is_complex:
+            raise ValueError(f'keep_mask of dtype {keep_mask.dtype}; expected bool or an integer type (nonzero = kept)')
+        shp = tuple(keep_mask.shape)
+        if shp == (B, H, W, D):
+            km = keep_mask
+        elif shp == (B, H, W) and shp == (H, W, D):
+            raise ValueError(f'keep_mask of shape {shp} is both (B, H, W) and (H, W, D) here; pass it as {(B, H, W, D)}')
+        elif shp == (B, H, W):
+            km = keep_mask[..., None]
+        elif shp == (H, W, D):
+            km = keep_mask[None]
+        elif shp == (H, W):
+            km = keep_mask[None, :, :, None]
+        else:
+            raise ValueError(f'keep_mask of shape {shp}; expected {(B, H, W, D)}, {(B, H, W)}, {(H, W, D)} or {(H, W)}')
+        keep = (km.to(xs.device) != 0).expand(B, H, W, D).clone()
+        start = min(max(int(start_loc[0]) * W + int(start_loc[1]), 0), H * W)
+        keep.view(B, H * W, D)[:, :start] = True
+        vmax = torch.tensor(self.vocab_size, dtype=torch.long, device=xs.device)
+        bad = (keep & ((xs < 0) | (xs >= vmax))).any()
+        host = torch.cat([(~keep.view(B, H * W, D).all(dim=0)).reshape(-1), bad.reshape(1)]).cpu()
+        if bool(host[-1]):
+            raise ValueError(f'keep_mask keeps a code outside 0 .. vocab_size - 1 (vocab_size = {self.vocab_size})')
+        return keep, host[:-1].view(H * W, D)
+
+    def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None):
         """``cached=False`` (transformers.py:352-356): nothing is carried from one step to the next -- every step recomputes the
         logits of the whole code map from the codes drawn so far (one teacher-forced pass of the engine per step, 256 per
         batch, as slow as the reference's own uncached loop) and samples position (h, w, d) from them with the draw the
@@ -349,15 +396,17 @@ class RQTransformer(Stage2Model):
         for pos in range(start, H * W):
             h, w = divmod(pos, W)
             for d in range(D):
+                if active is not None and not active[pos, d]:
+                    continue                             # keep_mask: the code is given in every row
                 logits = self._on_side_stream(xs.device, lambda: eng.logits(xs, cond, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
                 idx, _ = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], seed=seed,
                                                offset=offset + pos * D + d)
-                xs[:, h, w, d] = idx
+                xs[:, h, w, d] = idx if keep is None else torch.where(keep[:, h, w, d], xs[:, h, w, d], idx)
         return xs
 
-    def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list):
+    def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, keep=None, active=None):
         """``self.sampler = 'torch'`` (or RQAMD_SAMPLER=torch): the loop of transformers.py:346-364 driven from the host, one engine
         step per (h, w, d), the draw by ``torch.multinomial(probs, num_samples=1)`` on the filtered probabilities -- the call
         sample_from_logits makes (rqvae/utils/utils.py:112), so the device generator is consumed exactly as the reference consumes
@@ -367,18 +416,27 @@ class RQTransformer(Stage2Model):
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
         eng.step_begin(xs, cond, cbs)
-        for pos in range(H * W):
-            if pos < start:
+        n_pos = H * W
+        if active is not None:                         # keep_mask: nothing runs after the last position that draws a code
+            drawn = active.any(dim=1).nonzero()
+            n_pos = int(drawn[-1]) + 1 if len(drawn) else 0
+        for pos in range(n_pos):
+            if pos < start or (active is not None and not active[pos].any()):
                 eng.step_logits(pos, -1)               # given codes: body KV cache only
                 continue
+            h, w = divmod(pos, W)
             for d in range(D):
                 logits = eng.step_logits(pos, d)
+                if active is not None and not active[pos, d]:
+                    continue                           # given in every row: no draw (the step fed the head stack's KV cache)
                 _, probs = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], want_probs=True, want_samples=False)
                 try:
                     idx = torch.multinomial(probs, num_samples=1).squeeze(-1)
                 except RuntimeError:
                     print(probs, logits, torch.sum(probs), torch.sum(probs < 0))
                     raise
+                if keep is not None:
+                    idx = torch.where(keep[:, h, w, d], xs[:, h, w, d], idx)
                 eng.step_set_code(pos, d, idx)
         return eng.step_end()
 
