@@ -204,6 +204,29 @@ int rqamd_rqt_sample_masked(rqamd_rqt* h, const int64_t* partial, const uint8_t*
                             const int64_t* cond, int batch, const float* const* codebooks, float temperature,
                             const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
                             int use_graph, int64_t* codes_out, void* stream);
+/* Classifier-free guidance inside the engine (not in the reference); additive, ABI v7.  The `batch` images run as 2 * batch rows:
+ * row b under cond[b], row batch + b under uncond[b] (NULL = zeros, as for cond), both started from the same `partial` (and `keep`).
+ * At every step the classifier gives the logits of all 2 * batch rows; row b is then drawn from
+ *     g = guide(c, u, s) = (c == -inf) ? -inf : fmaf(s - 1, c - u, c),   c = logits[b], u = logits[batch + b], s = guidance_scale
+ * (fp32, raw logits, before the temperature; u + s (c - u), written so that s = 1 returns c bit for bit) with the temperature,
+ * top-k, top-p and Philox counter offset + pos * D + d of row b of an unguided call, and the code is written to both rows: the
+ * unconditional twin sees exactly what its conditional twin drew.  codes_out (batch,H,W,D): rows 0 .. batch - 1.
+ * Which GEMM and attention kernels a row takes follows the 2 * batch rows of the step; s = 1 runs the pairs like any other scale
+ * and returns what rqamd_rqt_sample over the 2 * batch rows (partial twice, cond then uncond) returns in its first half.
+ * keep / pos_active_host: as in rqamd_rqt_sample_masked (batch rows of flags; row b's flags hold for both twins), or NULL: nothing
+ * kept (pos_active_host is then ignored).  start_h / start_w as in rqamd_rqt_sample; a masked call passes 0, 0.
+ * Any finite guidance_scale is accepted (0 draws from the unconditional rows, negative values push away from cond); NaN or
+ * infinity: RQAMD_ERR_INVALID.  Guided calls replay captured graphs of their own (masked and unmasked), keyed on 2 * batch and on
+ * guidance_scale next to the fields of the unguided key: alternating with unguided calls recaptures nothing, a new scale recaptures
+ * the guided graphs only. */
+int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                            const int64_t* cond, const int64_t* uncond, int batch, const float* const* codebooks,
+                            int start_h, int start_w, float temperature, float guidance_scale, const int* top_k,
+                            const float* top_p, uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream);
+/* out[r][v] = guide(cond_logits[r][v], uncond_logits[r][v], scale) of rqamd_rqt_sample_guided, through the same device function:
+ * (rows, vocab) fp32, contiguous, device memory; vocab >= 1 (16-byte accesses when vocab % 4 == 0 and the three bases are aligned).
+ * For host-driven loops (rqamd_rqt_step_logits over 2 * batch rows) and for tests; the engine never materialises g. */
+int rqamd_guide_logits(const float* cond_logits, const float* uncond_logits, int rows, int vocab, float scale, float* out, void* stream);
 /* rqamd_rqt_logits <- the same cached_forward stepping (transformers.py:190-287) driven
  * teacher-forced over given codes, returning every step's logits: logits_out (batch,H,W,D,vocab) fp32.
  * This is the parity hook against RQTransformer.forward (transformers.py:113-188). */

@@ -91,11 +91,15 @@ struct rqamd_rqt {
     // graph cache
     // one captured position per 8-key bucket of the body context (the attention kernel variant is baked in); the last one is the catch-all of
     // contexts beyond 256 tokens: captured once with t_max = Tbody - 1, it serves every position from token 256 on (position_body)
-    // two sets: [0] unmasked sampling, [1] masked sampling (the sampler launches carry the keep-flag pointer, a kernel argument).
-    // Both are captured under the same key, so a caller that alternates between the two forms replays what it captured before
+    // four sets: [0] unmasked sampling, [1] masked sampling (the sampler launches carry the keep-flag pointer, a kernel argument),
+    // [2] / [3] the same two forms of guided sampling (rqamd_rqt_sample_guided: 2B rows, other sampler kernels).  The two sets of a
+    // family are captured under the same key, so a caller that alternates between the forms replays what it captured before.  The
+    // families have a key each (gkey[0] unguided, gkey[1] guided: B is the 2B rows of the engine and the guidance scale is part of
+    // it): a key change drops the two sets of its own family only (gstale), gvalid = false drops all four
     static constexpr int NGRAPH = 33;
-    hipGraphExec_t gexec[2][NGRAPH] = {};
-    struct Key { int B; float T; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey;
+    hipGraphExec_t gexec[4][NGRAPH] = {};
+    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey[2];
+    bool gkey_set[2] = {false, false}, gstale[2] = {false, false};
     bool gvalid = false;
 
     GemmProfile prof;
@@ -554,6 +558,9 @@ struct StepCtx {
     const float* top_p;
     bool sample;           // run the sampler (else teacher-forced)
     const uint8_t* keep;   // sampling: per-code keep flags (h->keep) of a masked call, or null
+    bool guided;           // guided sampling: B = 2 * Bs rows run up to the classifier (rows Bs.. are the unconditional twins of rows
+    int Bs;                //   0..Bs-1); the sampler runs over Bs rows, mixes the two logits rows of a pair and writes the code to both
+    float gscale;
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -645,6 +652,7 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
         s.logits = h->logits; s.rows = B; s.V = h->V; s.temperature = c.temperature; s.top_k = c.top_k[d]; s.top_p = c.top_p[d];
         s.redo = h->smp_redo; s.rng = h->rng; s.pos = h->st; s.d = d; s.D = h->D; s.out = h->xs; s.out_stride = (long)h->HW * h->D;
         s.keep = c.keep; s.keep_stride = s.out_stride;
+        if (c.guided) { s.rows = c.Bs; s.logits_u = h->logits + (long)c.Bs * h->V; s.gscale = c.gscale; s.out_mirror = (long)c.Bs * s.out_stride; }
         RQ_TRY(rq_launch_sample(s, st));
     } else if (c.logits_out) {
         float* dst = c.logits_out + ((long)host_pos * h->D + d) * h->V;
@@ -664,14 +672,23 @@ static int position_sequence(rqamd_rqt* h, const StepCtx& c, bool first_pos, boo
 }
 
 // inputs into the workspace, position counter to 0, conditioning prefix through the body stack
-static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const int64_t* cond, hipStream_t st) {
+// (guided sampling: `partial` and `cond` / `uncond` hold c.Bs rows each -- the codes go into both halves of h->xs, the two conditionings
+// into the two halves of h->cond)
+static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const int64_t* cond, hipStream_t st, const int64_t* uncond = nullptr) {
     const int B = c.B;
     h->step_on = false;                            // any new batch ends a stepping sequence (same workspace)
     RQ_TRY(ensure_batch(h, B));
     RQ_TRY(finalize_tables(h, st));
-    RQ_HIP(hipMemcpyAsync(h->xs, partial, (size_t)B * h->HW * h->D * 8, hipMemcpyDeviceToDevice, st));
-    if (cond) RQ_HIP(hipMemcpyAsync(h->cond, cond, (size_t)B * h->cond_len * 8, hipMemcpyDeviceToDevice, st));
-    else RQ_HIP(hipMemsetAsync(h->cond, 0, (size_t)B * h->cond_len * 8, st));
+    const int n_in = c.guided ? c.Bs : B;          // rows the caller gave
+    const size_t xb = (size_t)n_in * h->HW * h->D * 8, cb = (size_t)n_in * h->cond_len * 8;
+    RQ_HIP(hipMemcpyAsync(h->xs, partial, xb, hipMemcpyDeviceToDevice, st));
+    if (cond) RQ_HIP(hipMemcpyAsync(h->cond, cond, cb, hipMemcpyDeviceToDevice, st));
+    else RQ_HIP(hipMemsetAsync(h->cond, 0, cb, st));
+    if (c.guided) {
+        RQ_HIP(hipMemcpyAsync(h->xs + (size_t)n_in * h->HW * h->D, partial, xb, hipMemcpyDeviceToDevice, st));
+        if (uncond) RQ_HIP(hipMemcpyAsync(h->cond + (size_t)n_in * h->cond_len, uncond, cb, hipMemcpyDeviceToDevice, st));
+        else RQ_HIP(hipMemsetAsync(h->cond + (size_t)n_in * h->cond_len, 0, cb, st));
+    }
     RQ_TRY(rq_launch_set_int(h->st, 0, st));
     // Conditioning prefix (text tokens): tokens 0..cond_len-2 only fill the body KV cache (transformers.py:235-239; in
     // forward() their body outputs also feed cond_classifier, :150-153).  All P = cond_len-1 tokens of a chunk of images go
@@ -704,17 +721,21 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
 // per-position activity (null: every position).  An inactive position has every code given in every row: body stack only, like the
 // positions before start_idx.  Nothing runs after the last active position -- nobody reads its KV entries.
 static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, const int64_t* cond, int start_idx, bool use_graph,
-                   int64_t* codes_out, hipStream_t st, const uint8_t* keep = nullptr, const uint8_t* pos_active = nullptr) {
+                   int64_t* codes_out, hipStream_t st, const uint8_t* keep = nullptr, const uint8_t* pos_active = nullptr,
+                   const int64_t* uncond = nullptr) {
     StepCtx c = c_in;
-    const int B = c.B;
-    RQ_TRY(begin_batch(h, c, partial, cond, st));
+    const int n_in = c.guided ? c.Bs : c.B;              // rows of the caller's arrays (guided: the engine runs c.B = 2 * n_in rows)
+    RQ_TRY(begin_batch(h, c, partial, cond, st, uncond));
     int n_pos = h->HW;
     if (keep) {
-        RQ_HIP(hipMemcpyAsync(h->keep, keep, (size_t)B * h->HW * h->D, hipMemcpyDeviceToDevice, st));
+        const size_t kb = (size_t)n_in * h->HW * h->D;
+        RQ_HIP(hipMemcpyAsync(h->keep, keep, kb, hipMemcpyDeviceToDevice, st));
+        if (c.guided) RQ_HIP(hipMemcpyAsync(h->keep + kb, keep, kb, hipMemcpyDeviceToDevice, st));   // (the sampler reads rows 0..Bs-1)
         c.keep = h->keep;
         while (pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
     }
-    hipGraphExec_t* gexec = h->gexec[keep ? 1 : 0];
+    const int fam = c.guided ? 1 : 0;
+    hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = 0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
         const bool graphable = use_graph && c.sample && do_head && pos >= 1 && !h->prof.on;
@@ -722,6 +743,11 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
             if (!h->gvalid) {
                 for (auto& set : h->gexec) for (auto& g : set) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
                 h->gvalid = true;
+                h->gstale[0] = h->gstale[1] = false;
+            }
+            if (h->gstale[fam]) {                  // this family's key changed: its two sets go, the other family's stay
+                for (int f = 2 * fam; f < 2 * fam + 2; ++f) for (auto& g : h->gexec[f]) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+                h->gstale[fam] = false;
             }
             int bucket = (pos + h->cond_len - 1) >> 3;
             if (bucket >= rqamd_rqt::NGRAPH) bucket = rqamd_rqt::NGRAPH - 1;
@@ -754,27 +780,33 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         RQ_TRY(position_sequence(h, c, pos == 0, do_head, pos, st));
         RQ_TRY(rq_launch_add_int(h->st, 1, st));
     }
-    if (codes_out) RQ_HIP(hipMemcpyAsync(codes_out, h->xs, (size_t)B * h->HW * h->D * 8, hipMemcpyDeviceToDevice, st));
+    if (codes_out) RQ_HIP(hipMemcpyAsync(codes_out, h->xs, (size_t)n_in * h->HW * h->D * 8, hipMemcpyDeviceToDevice, st));
     return RQAMD_OK;
 }
 
-// rqamd_rqt_sample / rqamd_rqt_sample_masked behind their argument checks
+// rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided behind their argument checks.  `guided`: `batch` images run as
+// 2 * batch engine rows (rows batch.. conditioned on `uncond`), drawn from the guided logits with scale `gscale`
 static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active, const int64_t* cond, int batch,
                        const float* const* codebooks, int start_idx, float temperature, const int* top_k, const float* top_p,
-                       uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream) {
+                       uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream,
+                       bool guided = false, const int64_t* uncond = nullptr, float gscale = 1.f) {
     hipStream_t st = (hipStream_t)stream;
     h->step_on = false;
-    RQ_TRY(ensure_batch(h, batch));
+    const int rows = guided ? 2 * batch : batch;
+    RQ_TRY(ensure_batch(h, rows));
     StepCtx c{};
-    c.B = batch; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
-    // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their own)
+    c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
+    c.guided = guided; c.Bs = batch; c.gscale = gscale;
+    // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
+    // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
     rqamd_rqt::Key k{};
-    k.B = batch; k.T = temperature; k.stream = stream;
+    k.B = rows; k.T = temperature; k.gs = guided ? gscale : 0.f; k.guided = guided ? 1 : 0; k.stream = stream;
     for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; k.cb[d] = codebooks[d]; }
-    if (!h->gvalid || memcmp(&k, &h->gkey, sizeof(k)) != 0) { h->gvalid = false; h->gkey = k; }
+    const int fam = guided ? 1 : 0;
+    if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
-    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st, keep, pos_active));
+    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st, keep, pos_active, uncond));
     if (h->prof.on) {
         RQ_HIP(hipStreamSynchronize(st));
         double ms = 0;
@@ -824,6 +856,23 @@ extern "C" int rqamd_rqt_sample_masked(rqamd_rqt* h, const int64_t* partial, con
     if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: temperature must be > 0");
     return sample_impl(h, partial, keep, pos_active_host, cond, batch, codebooks, 0, temperature, top_k, top_p, seed, offset, use_graph,
                        codes_out, stream);
+}
+
+// Guided form (include/rqamd.h): classifier-free guidance inside the engine.  Image b runs twice, as row b under `cond` and as row
+// batch + b under `uncond`; at every step the sampler draws row b from guide(logits[b], logits[batch + b], guidance_scale) with the
+// filter and the Philox counter of row b of an unguided call, and writes the code to both rows -- the twin sees exactly what was drawn.
+extern "C" int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                                       const int64_t* cond, const int64_t* uncond, int batch, const float* const* codebooks,
+                                       int start_h, int start_w, float temperature, float guidance_scale, const int* top_k,
+                                       const float* top_p, uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream) {
+    if (!h || !partial || !codebooks || !top_k || !top_p || !codes_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: null argument");
+    if (batch < 1 || batch > 0x3fffffff) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: batch < 1 (or 2 * batch overflows)");
+    if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: temperature must be > 0");
+    if (!(guidance_scale - guidance_scale == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: guidance_scale must be finite");
+    int start_idx = start_h * h->cfg.W + start_w;
+    if (start_idx < 0) start_idx = 0;
+    return sample_impl(h, partial, keep, keep ? pos_active_host : nullptr, cond, batch, codebooks, start_idx, temperature, top_k, top_p, seed,
+                       offset, use_graph, codes_out, stream, true, uncond, guidance_scale);
 }
 
 extern "C" int rqamd_rqt_logits(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,

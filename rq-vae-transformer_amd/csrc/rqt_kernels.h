@@ -87,8 +87,14 @@ struct SampleArgs {
     int* redo;              // [rows] workspace: rows the top-k kernel hands to the general kernel (null: general kernel only)
     const uint8_t* keep;    // keep[row * keep_stride + (*pos * D + d)] != 0: the code is given -- no draw, `out` and `redo` untouched (null: draw every row)
     long keep_stride;
+    // classifier-free guidance (rqamd_rqt_sample_guided): row `row` is drawn from guide(logits[row], logits_u[row], gscale), mixed where
+    // the kernel loads the row -- no guided-logits buffer exists
+    const float* logits_u;  // [rows][V] logits of the unconditional twins, or null: unguided
+    float gscale;           // guidance scale s: g = c + (s - 1) (c - u)
+    long out_mirror;        // != 0: the drawn code is also written to out[(row * out_stride + slot) + out_mirror] (the twin's slot); 0: none
 };
 
+int rq_launch_guide_logits(const float* c, const float* u, int rows, int V, float scale, float* out, hipStream_t s);
 int rq_launch_resid_ln(const ResidLnArgs& a, hipStream_t s);
 int rq_launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s);
 int rq_launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s);

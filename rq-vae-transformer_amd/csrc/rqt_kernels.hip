@@ -13,6 +13,12 @@
 // 16777215.5 rounds to 2^24, u = 1, -log(u) = -0 and the exponential race divides by it.)
 static __device__ __forceinline__ float rq_u01(uint32_t r) { return fmaf((float)(r >> 9), 1.0f / 8388608.0f, 1.0f / 16777216.0f); }
 
+// rqt_sample_guided.hip compiles this file once more with RQ_SAMPLE_GUIDED_TU defined: only the sampler templates below and their
+// guided instantiations.  The guided kernels live in an object of their own because instantiating them next to the unguided ones
+// changes the code the compiler emits for sample_topk_kernel<false> (a module-level effect: register allocation of its top-k search),
+// and the unguided instruction stream is to stay as it is.
+#ifndef RQ_SAMPLE_GUIDED_TU
+
 template <int NS>
 __global__ __launch_bounds__(256) void resid_ln_kernel(ResidLnArgs p) {
     __shared__ float red[8];
@@ -1349,6 +1355,8 @@ int rq_launch_add_int(int* p, int v, hipStream_t s) {
     return rq_check_launch("add_int_kernel");
 }
 
+#endif  // !RQ_SAMPLE_GUIDED_TU
+
 // =================================================================================================
 // on-device sampler: temperature, top-k, NaN scrub, softmax, top-p, renormalise, one draw per row
 #ifndef RQ_SMP_NT             // A/B switch: the logits rows of sample_topk_kernel (read once) with the non-temporal policy
@@ -1443,6 +1451,25 @@ static __device__ __forceinline__ bool sample_kept(const SampleArgs& p, int row)
     return p.keep && p.keep[(long)row * p.keep_stride + (p.pos ? (*p.pos) * p.D + p.d : 0)] != 0;
 }
 
+// Classifier-free guidance: the logit a guided row is drawn from, u + s (c - u) written as c + (s - 1)(c - u) so that s = 1 returns c
+// bit for bit; a masked column (LogitMask: -inf in both rows) stays -inf instead of becoming inf - inf.  Raw logits, before the
+// temperature.  THE one place logits are mixed: the three samplers call it where they load their row, guide_logits_kernel for the
+// host paths.
+static __device__ __forceinline__ float guide_logit(float c, float u, float s) {
+    return c == -__int_as_float(0x7f800000) ? c : fmaf(s - 1.0f, c - u, c);
+}
+
+// The three samplers are templates on GUIDED.  <false>: the unguided kernels, whose instruction stream the parameter leaves as it was.
+// <true>: the row of p.logits_u is loaded next to the row of p.logits, the same way, and the two are mixed through guide_logit();
+// the drawn code also goes to the twin's slot (p.out_mirror).
+template <bool GUIDED>
+static __device__ __forceinline__ void sample_store(const SampleArgs& p, int row, int slot, int code) {
+    const long o = (long)row * p.out_stride + slot;
+    p.out[o] = (int64_t)code;
+    if (GUIDED && p.out_mirror) p.out[o + p.out_mirror] = (int64_t)code;
+}
+
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1457,7 +1484,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     const float* lg = p.logits + (long)row * V;
     const float NEG_INF = -__int_as_float(0x7f800000);
 
-    for (int i = tid; i < V; i += SMP_T) sx[i] = lg[i] / p.temperature;          // utils.py:96-97
+    if (GUIDED) {
+        const float* lu = p.logits_u + (long)row * V;
+        for (int i = tid; i < V; i += SMP_T) sx[i] = guide_logit(lg[i], lu[i], p.gscale) / p.temperature;
+    } else {
+        for (int i = tid; i < V; i += SMP_T) sx[i] = lg[i] / p.temperature;      // utils.py:96-97
+    }
     rq_syncthreads();
 
     // ---- top-k: radix-select the k-th largest key, drop everything strictly below it (utils.py:60-64)
@@ -1612,7 +1644,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
         for (int w = 1; w < SMP_T / 64; ++w)
             if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
         if (besti >= V) besti = 0;
-        p.out[(long)row * p.out_stride + slot] = (int64_t)besti;
+        sample_store<GUIDED>(p, row, slot, besti);
     }
 }
 
@@ -1660,7 +1692,7 @@ static __device__ __forceinline__ int blk_count_pp(int wave_cnt, SmpShared& sh, 
 }
 
 // softmax -> top-p -> renormalise -> (probs_out) -> draw, on NV scaled logits per thread (absent entries: idx < 0)
-template <int NV, typename IdxF>
+template <bool GUIDED, int NV, typename IdxF>
 static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&q)[NV], IdxF idx_of, int row, SmpShared& sh) {
     const int tid = threadIdx.x, V = p.V;
     const float NEG_INF = -__int_as_float(0x7f800000);
@@ -1783,10 +1815,11 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
         for (int w = 1; w < SMP_T / 64; ++w)
             if (sh.red[w] > best || (sh.red[w] == best && sh.redi[w] < besti)) { best = sh.red[w]; besti = sh.redi[w]; }
         if (besti >= V) besti = 0;
-        p.out[(long)row * p.out_stride + slot] = (int64_t)besti;
+        sample_store<GUIDED>(p, row, slot, besti);
     }
 }
 
+template <bool GUIDED>
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
@@ -1800,10 +1833,20 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     for (int j = 0; j < SMP_VPT / 4; ++j) {
         const int i4 = tid + SMP_T * j;
 #if RQ_SMP_NT
-        const f32x4 v = __builtin_nontemporal_load((const f32x4*)(lg + (long)(i4 < V4 ? i4 : V4 - 1) * 4));
+        f32x4 v = __builtin_nontemporal_load((const f32x4*)(lg + (long)(i4 < V4 ? i4 : V4 - 1) * 4));
 #else
-        const f32x4 v = *(const f32x4*)(lg + (long)(i4 < V4 ? i4 : V4 - 1) * 4);
+        f32x4 v = *(const f32x4*)(lg + (long)(i4 < V4 ? i4 : V4 - 1) * 4);
 #endif
+        if (GUIDED) {
+            const float* lu = p.logits_u + (long)row * V;
+#if RQ_SMP_NT
+            const f32x4 vu = __builtin_nontemporal_load((const f32x4*)(lu + (long)(i4 < V4 ? i4 : V4 - 1) * 4));
+#else
+            const f32x4 vu = *(const f32x4*)(lu + (long)(i4 < V4 ? i4 : V4 - 1) * 4);
+#endif
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = guide_logit(v[e], vu[e], p.gscale);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float x = scale ? v[e] / p.temperature : v[e];            // utils.py:96-97
@@ -1897,7 +1940,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
         qi[k] = s < total ? sh.idx[s] : -1;
     }
     rq_syncthreads();
-    sample_tail<SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
+    sample_tail<GUIDED, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
 }
 
 // Unfiltered draw (top_k covers the vocabulary, top_p >= 1: the reference's defaults, transformers.py:309-323):
@@ -1905,6 +1948,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
 // Gumbel_i = -log(-log u_i) from the same Philox counters as sample_kernel -- no max / sum reductions, no
 // LDS copy of the row, so occupancy is set by registers only (the general kernel holds V floats in LDS:
 // 2 workgroups per CU, 830 us per call at 4096 x 16384; this one is bound by reading the logits once).
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
@@ -1927,6 +1971,19 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = (i4 * 4 + e < V) ? lg[i4 * 4 + e] : NEG_INF;
+        }
+        if (GUIDED) {
+            const float* lu = p.logits_u + (long)row * V;
+            float w[4];
+            if (vec) {
+                const f32x4 q = *(const f32x4*)(lu + i4 * 4);
+                w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = (i4 * 4 + e < V) ? lu[i4 * 4 + e] : NEG_INF;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = guide_logit(v[e], w[e], p.gscale);
         }
         unsigned r[4];
         philox4x32_10((unsigned)i4, (unsigned)row, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
@@ -1953,35 +2010,78 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
         for (int w = 1; w < 4; ++w)
             if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
         if (besti >= V) besti = 0;
-        p.out[(long)row * p.out_stride + slot] = (int64_t)besti;
+        sample_store<GUIDED>(p, row, slot, besti);
     }
 }
 
-int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+// the launch sequence of one sampling step, for the unguided (this object) or the guided kernels (rqt_sample_guided.hip)
+template <bool GUIDED>
+static int launch_sample(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!(a.temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: temperature must be > 0");
+    if (GUIDED && !(a.gscale - a.gscale == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: guidance scale must be finite");
     if ((a.top_k <= 0 || a.top_k >= a.V) && (a.top_p < 0.f || a.top_p >= 1.0f) && !a.probs_out && a.out) {
-        RQ_LAUNCH(sample_gumbel_kernel, dim3(a.rows), dim3(256), 0, s, a);
+        RQ_LAUNCH(sample_gumbel_kernel<GUIDED>, dim3(a.rows), dim3(256), 0, s, a);
         return rq_check_launch("sample_gumbel_kernel");
     }
     const size_t smem = (size_t)a.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)sample_kernel<GUIDED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     SampleArgs b = a;
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch
     if (a.top_k > 0 && a.top_k < a.V && a.V <= SMP_T * SMP_VPT && a.V % 4 == 0 && a.redo && !env_lds_only) {
         // top-k on: register-resident kernel; rows it cannot finish (more than SMP_CAP keys tied into the top k, NaN
         // threshold) are flagged in a.redo and redone by the general kernel, whose other workgroups exit at once
-        RQ_LAUNCH(sample_topk_kernel, dim3(a.rows), dim3(SMP_T), 0, s, a);
+        RQ_LAUNCH(sample_topk_kernel<GUIDED>, dim3(a.rows), dim3(SMP_T), 0, s, a);
         RQ_TRY(rq_check_launch("sample_topk_kernel"));
     } else {
         b.redo = nullptr;
     }
-    RQ_LAUNCH(sample_kernel, dim3(a.rows), dim3(SMP_T), smem, s, b);
+    RQ_LAUNCH(sample_kernel<GUIDED>, dim3(a.rows), dim3(SMP_T), smem, s, b);
     return rq_check_launch("sample_kernel");
 }
+
+#ifdef RQ_SAMPLE_GUIDED_TU
+int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s) { return launch_sample<true>(a, s); }
+#else
+int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s);     // rqt_sample_guided.hip
+int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+    return a.logits_u ? rq_launch_sample_guided(a, s) : launch_sample<false>(a, s);
+}
+
+// g = guide(c, u, s) materialised, for the host paths (cached=False, sampler='torch') and the tests -- never inside the engine's
+// step, where the samplers mix the two rows as they load them.  16-byte loads where every row starts on one (V % 4 == 0, aligned
+// bases), scalar otherwise; any V >= 1.
+__global__ __launch_bounds__(256) void guide_logits_kernel(const float* c, const float* u, float* out, long n, int vec, float s) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (vec) {
+        if (i * 4 >= n) return;
+        const f32x4 a = *(const f32x4*)(c + i * 4), b = *(const f32x4*)(u + i * 4);
+        f32x4 g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = guide_logit(a[e], b[e], s);
+        *(f32x4*)(out + i * 4) = g;
+    } else {
+        if (i >= n) return;
+        out[i] = guide_logit(c[i], u[i], s);
+    }
+}
+int rq_launch_guide_logits(const float* c, const float* u, int rows, int V, float scale, float* out, hipStream_t s) {
+    if (!c || !u || !out || rows < 0 || V < 1) return rq_fail(RQAMD_ERR_INVALID, "guide_logits: bad argument");
+    if (!(scale - scale == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "guide_logits: scale must be finite");
+    if (rows == 0) return RQAMD_OK;
+    const long n = (long)rows * V;
+    const int vec = V % 4 == 0 && (((uintptr_t)c | (uintptr_t)u | (uintptr_t)out) & 15) == 0;
+    const long nt = vec ? n / 4 : n;
+    RQ_LAUNCH(guide_logits_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, c, u, out, n, vec, scale);
+    return rq_check_launch("guide_logits_kernel");
+}
+extern "C" int rqamd_guide_logits(const float* cond_logits, const float* uncond_logits, int rows, int vocab, float scale, float* out, void* stream) {
+    return rq_launch_guide_logits(cond_logits, uncond_logits, rows, vocab, scale, out, (hipStream_t)stream);
+}
+
 // one unfiltered multinomial draw per row of `logits` (rows x vocab, contiguous) -> out[row * out_stride]; used by the
 // stochastic soft codes of the quantiser (csrc/quantize.hip)
 int rq_launch_sample_rows(const float* logits, int rows, int vocab, uint64_t seed, uint64_t offset, int64_t* out, long out_stride, hipStream_t s) {
@@ -2258,3 +2358,4 @@ int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
     RQ_LAUNCH(log_prob_kernel, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
     return rq_check_launch("log_prob_kernel");
 }
+#endif  // !RQ_SAMPLE_GUIDED_TU

@@ -4,6 +4,7 @@ reference's ``rqvae.models`` API and the gfx950 kernels.
 There is no CPU path: if the library (or a GPU tensor) is missing this module raises.  PyTorch is used
 for device memory and streams only; every argument crossing the ABI is a raw pointer / size."""
 import contextlib
+import math
 import ctypes as C
 import os
 
@@ -78,6 +79,10 @@ _SIGS = {
     'rqamd_rqt_sample_masked': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
                                           C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_guided': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_guide_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward_onepass': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -334,6 +339,20 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, offse
                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(samples), ptr(probs),
                                         ptr(flags), stream_of(logits)))
     return samples, probs
+
+
+def guide_logits(c, u, scale):
+    """rqamd_guide_logits: classifier-free guidance on raw logits, g = c + (scale - 1) (c - u) with -inf of `c` kept (the device function
+    the guided samplers apply inside the engine).  c, u (rows, vocab) fp32, contiguous, same shape -> g (rows, vocab) fp32."""
+    if c.dim() != 2 or tuple(u.shape) != tuple(c.shape):
+        raise ValueError(f'guide_logits: logits of shapes {tuple(c.shape)} and {tuple(u.shape)}; expected two equal (rows, vocab)')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'guide_logits: scale {scale} is not finite')
+    rows, vocab = c.shape
+    out = torch.empty_like(c)
+    with on_device_of(c):
+        check(lib().rqamd_guide_logits(ptr(c, torch.float32), ptr(u, torch.float32), rows, vocab, float(scale), ptr(out), stream_of(c)))
+    return out
 
 
 def dbg_gemm(a_bf16, w_bf16, bias=None, epi=3, bm=0, bn=0, splitk=0, out=None):
@@ -627,6 +646,40 @@ class RqtEngine(_Engine):
         cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
         self._run(lambda: self._L.rqamd_rqt_sample_masked(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), B, cbs,
                                                         float(temperature), tk, tp, int(seed) & (2 ** 64 - 1),
+                                                        int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
+        return out
+
+    def sample_guided(self, partial, keep, pos_active, cond, uncond, codebooks, start_loc, temperature, guidance_scale, top_k, top_p,
+                      seed, offset, use_graph):
+        """rqamd_rqt_sample_guided: classifier-free guidance over the B images of `partial` (2B engine rows; rows B.. conditioned on
+        `uncond`, None = zeros as for `cond`).  `keep` / `pos_active` as in sample_masked, or None: nothing kept."""
+        self._check(partial, cond, codebooks)
+        if uncond is not None:
+            want = (partial.shape[0], max(self.cfg.block_size_cond, 1))
+            if tuple(uncond.shape) != want:
+                raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {want}')
+            self._on_my_device(uncond)
+        if not math.isfinite(float(guidance_scale)):
+            raise ValueError(f'guidance_scale {guidance_scale} is not finite')
+        kp = None
+        if keep is not None:
+            if keep.dtype != torch.uint8 or tuple(keep.shape) != tuple(partial.shape):
+                raise ValueError(f'keep of shape {tuple(keep.shape)} / {keep.dtype}; expected {tuple(partial.shape)} / torch.uint8')
+            self._on_my_device(keep)
+            kp = ptr(keep, torch.uint8)
+        B = partial.shape[0]
+        c = self.cfg
+        pa = None
+        if pos_active is not None:
+            if len(pos_active) != c.H * c.W:
+                raise ValueError(f'pos_active has {len(pos_active)} entries; expected {c.H * c.W}')
+            pa = (C.c_uint8 * (c.H * c.W))(*[1 if a else 0 for a in pos_active])
+        out = torch.empty_like(partial)
+        D = c.D
+        cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
+        self._run(lambda: self._L.rqamd_rqt_sample_guided(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64),
+                                                        ptr(uncond, torch.int64), B, cbs, int(start_loc[0]), int(start_loc[1]),
+                                                        float(temperature), float(guidance_scale), tk, tp, int(seed) & (2 ** 64 - 1),
                                                         int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
         return out
 

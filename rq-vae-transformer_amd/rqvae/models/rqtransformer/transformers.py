@@ -12,6 +12,7 @@ softmax / logits are fp32 either way.  Arguments of ``sample`` that cannot mean 
 are never ignored silently: ``cached=False`` runs a real uncached loop (every step recomputes all logits; the reference's own
 cross-check of its cache, transformers.py:352-356); ``is_tqdm`` / ``desc`` have nothing to report on (the
 whole loop is one asynchronous C call) and ``fast`` is unused by the reference itself."""
+import math
 import os
 from collections import OrderedDict
 
@@ -306,22 +307,7 @@ class RQTransformer(Stage2Model):
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
-        if top_k is None:
-            top_k_list = [self.vocab_size[i] for i in range(D)]
-        elif isinstance(top_k, int):
-            top_k_list = [min(top_k, self.vocab_size[i]) for i in range(D)]
-        elif len(top_k) == 1:
-            top_k_list = [min(top_k[0], self.vocab_size[i]) for i in range(D)]
-        else:
-            top_k_list = [min(top_k[i], self.vocab_size[i]) for i in range(D)]
-        if top_p is None:
-            top_p_list = [1.0 for _ in range(D)]
-        elif isinstance(top_p, float):
-            top_p_list = [min(top_p, 1.0) for _ in range(D)]
-        elif len(top_p) == 1:
-            top_p_list = [min(top_p[0], 1.0) for _ in range(D)]
-        else:
-            top_p_list = [min(top_p[i], 1.0) for i in range(D)]
+        top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
         eng = self._eng(amp)                            # amp=True: the fp16 build of the engine (the reference's fp16 autocast)
@@ -348,6 +334,78 @@ class RQTransformer(Stage2Model):
         out = self._on_side_stream(device, lambda: eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list,
                                                               seed, offset, self.use_graph))
         return out
+
+    def _filter_lists(self, top_k, top_p):
+        """top_k / top_p of sample() -> one value per depth (transformers.py:309-323)"""
+        D = self.block_size[2]
+        if top_k is None:
+            top_k_list = [self.vocab_size[i] for i in range(D)]
+        elif isinstance(top_k, int):
+            top_k_list = [min(top_k, self.vocab_size[i]) for i in range(D)]
+        elif len(top_k) == 1:
+            top_k_list = [min(top_k[0], self.vocab_size[i]) for i in range(D)]
+        else:
+            top_k_list = [min(top_k[i], self.vocab_size[i]) for i in range(D)]
+        if top_p is None:
+            top_p_list = [1.0 for _ in range(D)]
+        elif isinstance(top_p, float):
+            top_p_list = [min(top_p, 1.0) for _ in range(D)]
+        elif len(top_p) == 1:
+            top_p_list = [min(top_p[0], 1.0) for _ in range(D)]
+        else:
+            top_p_list = [min(top_p[i], 1.0) for i in range(D)]
+        return top_k_list, top_p_list
+
+    @torch.no_grad()
+    def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
+                      amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, uncond=None, guidance_scale=1.0,
+                      keep_mask=None):
+        """sample() with classifier-free guidance (not in the reference): every code is drawn from the guided logits
+        g = u + s (c - u), c / u the raw logits of the image under `cond` / under `uncond` (same shape and dtype rules as `cond`;
+        None = zeros, as cond=None), s = `guidance_scale` (any finite value; 1: the conditional logits, bit for bit).  The loop runs
+        inside the engine over 2B rows (rqamd_rqt_sample_guided): the unconditional twin of an image sees exactly the codes its
+        conditional twin drew, and row b uses the temperature, top-k, top-p and Philox counter of row b of sample().  Returns
+        (B,H,W,D) int64.  ``keep_mask`` composes as in sample(); ``cached=False`` and ``sampler='torch'`` are the host loops of
+        sample() over the 2B rows, the former bit for bit equal to ``cached=True``."""
+        assert self.block_size == partial_sample.shape[1:]
+        self._cf = None
+        (H, W, D) = self.block_size
+        if not math.isfinite(float(guidance_scale)):
+            raise ValueError(f'guidance_scale {guidance_scale} is not finite')
+        scale = float(guidance_scale)
+        top_k_list, top_p_list = self._filter_lists(top_k, top_p)
+        B = partial_sample.shape[0]
+        device = partial_sample.device
+        if uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
+            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+        eng = self._eng(amp)
+        cbs = self._checked_codebooks(model_aux)
+        xs = partial_sample.to(torch.long).contiguous()
+        c, u = self._cond(cond, B, device), self._cond(uncond, B, device)
+        keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
+        if self.sampler == 'torch' or not cached:
+            if self.sampler == 'torch' and not cached:
+                raise NotImplementedError("sampler='torch' steps the cached engine; cached=False is available with the default sampler")
+            if keep is not None:
+                xs = torch.where(keep, xs, torch.zeros_like(xs))            # (see sample(): the host loops embed every code)
+            # the host loops run the engine's unguided entry points over the 2B rows themselves: images under cond, then their twins
+            xs2 = torch.cat([xs, xs])
+            c2 = None
+            if c is not None or u is not None:
+                zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
+                c2 = torch.cat([zeros if c is None else c, zeros if u is None else u])
+            if self.sampler == 'torch':
+                return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, keep, active, scale)
+            seed, offset = self._draw_rng(device, H * W * D)
+            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active, scale)
+        seed, offset = self._draw_rng(device, H * W * D)
+        keep8, pos_active, start = None, None, start_loc
+        if keep is not None:
+            keep8 = keep.to(torch.uint8).contiguous()
+            pos_active = [bool(a) for a in active.any(dim=1).tolist()]
+            start = (0, 0)                                                   # (the kept prefix is part of `keep`)
+        return self._on_side_stream(device, lambda: eng.sample_guided(xs, keep8, pos_active, c, u, cbs, start, temperature, scale,
+                                                                      top_k_list, top_p_list, seed, offset, self.use_graph))
 
     def _keep_flags(self, keep_mask, xs, start_loc):
         """keep_mask of sample() -> (keep (B,H,W,D) bool on the device of `xs`, active (H*W, D) bool on the host: some row draws that
@@ -381,18 +439,23 @@ class RQTransformer(Stage2Model):
             raise ValueError(f'keep_mask keeps a code outside 0 .. vocab_size - 1 (vocab_size = {self.vocab_size})')
         return keep, host[:-1].view(H * W, D)
 
-    def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None):
+    def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None,
+                         guidance_scale=None):
         """``cached=False`` (transformers.py:352-356): nothing is carried from one step to the next -- every step recomputes the
         logits of the whole code map from the codes drawn so far (one teacher-forced pass of the engine per step, 256 per
         batch, as slow as the reference's own uncached loop) and samples position (h, w, d) from them with the draw the
         cached path would make at that step (same Philox key: seed, offset + step).  It exists, as in the reference, as the
         cross-check of the cache: the codes equal ``cached=True`` bit for bit (tests/test_gpu_parity.py).  (Both paths step the
         engine with B rows per launch -- the teacher-forced pass is the cached stepping over given codes, not one (B*H*W*D)-row
-        pass -- so both pick the same kernels for a given B)"""
+        pass -- so both pick the same kernels for a given B)
+        ``guidance_scale`` (sample_guided): `xs` / `cond` hold 2B rows, images then their unconditional twins; each step draws B rows
+        from guide_logits of the two halves -- Philox row b, as the engine's guided sampler -- and writes the code to both halves;
+        `keep` has B rows and the first B rows are returned."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
         xs = xs.clone()
+        n = xs.shape[0] // 2 if guidance_scale is not None else xs.shape[0]
         for pos in range(start, H * W):
             h, w = divmod(pos, W)
             for d in range(D):
@@ -401,20 +464,28 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(xs.device, lambda: eng.logits(xs, cond, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
+                if guidance_scale is not None:
+                    logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
                 idx, _ = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], seed=seed,
                                                offset=offset + pos * D + d)
-                xs[:, h, w, d] = idx if keep is None else torch.where(keep[:, h, w, d], xs[:, h, w, d], idx)
-        return xs
+                if keep is not None:
+                    idx = torch.where(keep[:, h, w, d], xs[:n, h, w, d], idx)
+                xs[:, h, w, d] = idx if guidance_scale is None else torch.cat([idx, idx])
+        return xs if guidance_scale is None else xs[:n].contiguous()
 
-    def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, keep=None, active=None):
+    def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, keep=None, active=None,
+                                  guidance_scale=None):
         """``self.sampler = 'torch'`` (or RQAMD_SAMPLER=torch): the loop of transformers.py:346-364 driven from the host, one engine
         step per (h, w, d), the draw by ``torch.multinomial(probs, num_samples=1)`` on the filtered probabilities -- the call
         sample_from_logits makes (rqvae/utils/utils.py:112), so the device generator is consumed exactly as the reference consumes
         it (one multinomial over a (B, V) tensor per step).  ~10x slower than the default on-device sampler (no graphs, one host
-        round per step); meant for seed-for-seed comparisons, not for throughput."""
+        round per step); meant for seed-for-seed comparisons, not for throughput.
+        ``guidance_scale`` (sample_guided): 2B rows are stepped, images then their unconditional twins; the B draws of a step come
+        from guide_logits of the two halves and are set in both; `keep` has B rows and the first B rows are returned."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
+        n = xs.shape[0] // 2 if guidance_scale is not None else xs.shape[0]
         eng.step_begin(xs, cond, cbs)
         n_pos = H * W
         if active is not None:                         # keep_mask: nothing runs after the last position that draws a code
@@ -429,6 +500,8 @@ class RQTransformer(Stage2Model):
                 logits = eng.step_logits(pos, d)
                 if active is not None and not active[pos, d]:
                     continue                           # given in every row: no draw (the step fed the head stack's KV cache)
+                if guidance_scale is not None:
+                    logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
                 _, probs = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], want_probs=True, want_samples=False)
                 try:
                     idx = torch.multinomial(probs, num_samples=1).squeeze(-1)
@@ -436,9 +509,10 @@ class RQTransformer(Stage2Model):
                     print(probs, logits, torch.sum(probs), torch.sum(probs < 0))
                     raise
                 if keep is not None:
-                    idx = torch.where(keep[:, h, w, d], xs[:, h, w, d], idx)
-                eng.step_set_code(pos, d, idx)
-        return eng.step_end()
+                    idx = torch.where(keep[:, h, w, d], xs[:n, h, w, d], idx)
+                eng.step_set_code(pos, d, idx if guidance_scale is None else torch.cat([idx, idx]))
+        out = eng.step_end()
+        return out if guidance_scale is None else out[:n].contiguous()
 
     @staticmethod
     def _draw_rng(device, n_steps):
