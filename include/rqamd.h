@@ -115,6 +115,17 @@ int rqamd_rq_embed(const int64_t* codes, const float* const* codebooks, const in
 int rqamd_sample_logits(const float* logits, int rows, int vocab, float temperature, int top_k,
                         float top_p, uint64_t seed, uint64_t offset, int64_t* samples_out,
                         float* probs_out, int* row_flags, void* stream);
+/* rqamd_sample_logits with a temperature, top-k and top-p per row (not in the reference); additive, ABI v7.  temperature, top_k,
+ * top_p: DEVICE arrays of `rows` entries; seeds: a device array of `rows` Philox keys, or NULL.  Row r is filtered and drawn exactly
+ * as row r of rqamd_sample_logits(logits, rows, vocab, temperature[r], top_k[r], top_p[r], seed, offset, ...) over the same matrix
+ * and the same row_flags -- samples_out and probs_out bit for bit, whichever of the three sampler kernels that call would take.
+ * With seeds, row r draws with key seeds[r] and Philox row 0 instead: what row 0 of the one-row call
+ * rqamd_sample_logits(logits + r * vocab, 1, ..., seeds[r], offset, ...) draws, wherever the row stands in the matrix (seed is
+ * then unused).  top_k[r] <= 0 or >= vocab and top_p[r] < 0 mean "off", as above.  Nothing is read on the host and no state is
+ * kept: the caller validates temperature > 0 (the kernels trap on no value; a temperature <= 0 or NaN draws an arbitrary code). */
+int rqamd_sample_logits_rows(const float* logits, int rows, int vocab, const float* temperature, const int* top_k,
+                             const float* top_p, const uint64_t* seeds, uint64_t seed, uint64_t offset,
+                             int64_t* samples_out, float* probs_out, int* row_flags, void* stream);
 
 /* ---- RQ-VAE encoder / decoder engine -------------------------------------------------------
  * Handle = packed bf16 weights + activation workspace for Encoder/Decoder (modules.py:10-202),
@@ -227,6 +238,29 @@ int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, const uint8_t*
  * (rows, vocab) fp32, contiguous, device memory; vocab >= 1 (16-byte accesses when vocab % 4 == 0 and the three bases are aligned).
  * For host-driven loops (rqamd_rqt_step_logits over 2 * batch rows) and for tests; the engine never materialises g. */
 int rqamd_guide_logits(const float* cond_logits, const float* uncond_logits, int rows, int vocab, float scale, float* out, void* stream);
+/* Sampling parameters per image (not in the reference); additive, ABI v7.  One entry point for plain, masked and guided sampling:
+ * keep NULL: unmasked (pos_active_host is ignored), else as in rqamd_rqt_sample_masked; uncond NULL and guidance_scale NULL: unguided,
+ * else as in rqamd_rqt_sample_guided (uncond NULL = zeros; uncond without guidance_scale is RQAMD_ERR_INVALID).
+ * HOST arrays, read before the call returns: temperature (batch), top_k and top_p (batch * D, image-major: [b * D + d]),
+ * guidance_scale (batch) or NULL, seeds (batch) or NULL.  Every temperature must be > 0 and finite and every scale finite, else
+ * RQAMD_ERR_INVALID; top_k <= 0 or >= vocab and top_p < 0 mean "off" (top_p = 1.0 keeps every token), as elsewhere.
+ * Image b is drawn exactly as the scalar entry point draws row b of the same batch with b's values: the same logits, the sampler
+ * kernel those values select, the same Philox counters -- bit for bit, whatever the other rows ask for.
+ * seeds NULL: key `seed`, counter offset + pos * D + d and Philox row b, as in the scalar calls.  seeds given: image b draws with key
+ * seeds[b], Philox row 0 and counter pos * D + d, the stream of row 0 of a scalar call seeded with seeds[b] at offset 0, wherever the
+ * image stands in the batch (seed / offset are then unused).
+ * The values live in device buffers of the handle that the sampler kernels read, so the captured graphs of per-row calls (four sets
+ * of their own: plain, masked, guided, guided + masked; four more for calls with seeds, whose sampler launches take their key from
+ * another buffer) are keyed on rows, codebooks, stream and the guided flag only: a call with other values replays them, and scalar,
+ * per-row and seeded per-row calls never invalidate or replay each other's graphs. */
+int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                          const int64_t* cond, const int64_t* uncond, int batch, const float* const* codebooks,
+                          int start_h, int start_w, const float* temperature, const int* top_k, const float* top_p,
+                          const float* guidance_scale, const uint64_t* seeds, uint64_t seed, uint64_t offset,
+                          int use_graph, int64_t* codes_out, void* stream);
+/* *captures = the number of position graphs this handle has captured so far (every form of sampling); a call that replays only
+ * leaves it unchanged. */
+int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures);
 /* rqamd_rqt_logits <- the same cached_forward stepping (transformers.py:190-287) driven
  * teacher-forced over given codes, returning every step's logits: logits_out (batch,H,W,D,vocab) fp32.
  * This is the parity hook against RQTransformer.forward (transformers.py:113-188). */

@@ -83,6 +83,13 @@ struct rqamd_rqt {
     uint64_t* rng;      // {seed, offset}
     int* smp_redo;      // [rows] sampler workspace (rows the top-k kernel hands back to the general kernel)
     uint8_t* keep;      // [rows][HW][D] keep flags of a masked sampling call (rqamd_rqt_sample_masked), laid out like xs
+    // per-row sampling parameters of rqamd_rqt_sample_rows, filled before the position loop of every such call (outside any capture): the
+    // captured per-row graphs hold these addresses, never a value
+    float *row_T, *row_gs;      // [rows]
+    int* row_tk;                // [rows][D]
+    float* row_tp;              // [rows][D]
+    uint64_t* row_seed;         // [rows]
+    std::vector<char> row_host; // host staging of the five arrays: outlives the asynchronous copies of the call that filled it
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -95,12 +102,20 @@ struct rqamd_rqt {
     // [2] / [3] the same two forms of guided sampling (rqamd_rqt_sample_guided: 2B rows, other sampler kernels).  The two sets of a
     // family are captured under the same key, so a caller that alternates between the forms replays what it captured before.  The
     // families have a key each (gkey[0] unguided, gkey[1] guided: B is the 2B rows of the engine and the guidance scale is part of
-    // it): a key change drops the two sets of its own family only (gstale), gvalid = false drops all four
+    // it): a key change drops the two sets of its own family only (gstale), gvalid = false drops all of them.
+    // [4] .. [7]: the same four forms of per-row calls (rqamd_rqt_sample_rows), families gkey[2] unguided and gkey[3] guided, and
+    // [8] .. [11] (gkey[4], gkey[5]) those of per-row calls with per-image seeds: whether the sampler reads h->row_seed or h->rng is a
+    // kernel argument of the captured launch, so seeded calls must never replay unseeded graphs, and neither recaptures the other's.  Their
+    // sampler launches read every parameter from h->row_*, so their keys hold no parameter value (T, gs, tk, tp stay zero): rows,
+    // codebooks, stream and the guided flag only, and a call with other values replays what is there.  Scalar and per-row families
+    // never invalidate each other.
     static constexpr int NGRAPH = 33;
-    hipGraphExec_t gexec[4][NGRAPH] = {};
-    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey[2];
-    bool gkey_set[2] = {false, false}, gstale[2] = {false, false};
+    static constexpr int NFAM = 6;
+    hipGraphExec_t gexec[2 * NFAM][NGRAPH] = {};
+    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey[NFAM];
+    bool gkey_set[NFAM] = {}, gstale[NFAM] = {};
     bool gvalid = false;
+    int64_t n_capture = 0;     // position graphs captured over the life of the handle (rqamd_rqt_graph_captures)
 
     GemmProfile prof;
 
@@ -396,7 +411,8 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     const size_t rows = brows > prow ? brows : prow;              // activation rows (decode step or prefill chunk)
     size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + al(brows * V * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
                    + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4)
-                   + al(brows * h->HW * h->D);
+                   + al(brows * h->HW * h->D)
+                   + 2 * al(brows * 4) + 2 * al(brows * h->D * 4) + al(brows * 8);
     RQ_TRY(h->ws.reserve(total));
     char* p = (char*)h->ws.p;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
@@ -409,6 +425,9 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     h->xs = (int64_t*)take(brows * h->HW * h->D * 8); h->cond = (int64_t*)take(brows * h->cond_len * 8);
     h->st = (int*)take(64); h->rng = (uint64_t*)take(64); h->smp_redo = (int*)take(brows * 4);
     h->keep = (uint8_t*)take(brows * h->HW * h->D);
+    h->row_T = (float*)take(brows * 4); h->row_gs = (float*)take(brows * 4);
+    h->row_tk = (int*)take(brows * h->D * 4); h->row_tp = (float*)take(brows * h->D * 4);
+    h->row_seed = (uint64_t*)take(brows * 8);
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
     const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
     // (8-bit keys: half the bytes for K plus one fp32 scale per (row, head, position))
@@ -561,6 +580,8 @@ struct StepCtx {
     bool guided;           // guided sampling: B = 2 * Bs rows run up to the classifier (rows Bs.. are the unconditional twins of rows
     int Bs;                //   0..Bs-1); the sampler runs over Bs rows, mixes the two logits rows of a pair and writes the code to both
     float gscale;
+    bool per_row;          // rqamd_rqt_sample_rows: the sampler reads temperature / top_k / top_p (and gscale when guided) of each row from
+    bool row_seeds;        //   h->row_*, and with row_seeds the Philox key from h->row_seed; the scalars above are unused
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -653,6 +674,12 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
         s.redo = h->smp_redo; s.rng = h->rng; s.pos = h->st; s.d = d; s.D = h->D; s.out = h->xs; s.out_stride = (long)h->HW * h->D;
         s.keep = c.keep; s.keep_stride = s.out_stride;
         if (c.guided) { s.rows = c.Bs; s.logits_u = h->logits + (long)c.Bs * h->V; s.gscale = c.gscale; s.out_mirror = (long)c.Bs * s.out_stride; }
+        if (c.per_row) {       // rows 0 .. Bs-1 of the tables, for both twins of a guided pair
+            s.temperature = 1.f; s.top_k = 0; s.top_p = -1.f;
+            s.row_temperature = h->row_T; s.row_top_k = h->row_tk; s.row_top_p = h->row_tp;
+            s.row_gscale = c.guided ? h->row_gs : nullptr;
+            if (c.row_seeds) { s.row_seeds = h->row_seed; s.rng = nullptr; }      // key row_seed[b], counter 0 + slot (s.offset is 0)
+        }
         RQ_TRY(rq_launch_sample(s, st));
     } else if (c.logits_out) {
         float* dst = c.logits_out + ((long)host_pos * h->D + d) * h->V;
@@ -734,7 +761,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         c.keep = h->keep;
         while (pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
     }
-    const int fam = c.guided ? 1 : 0;
+    const int fam = (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = 0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
@@ -743,7 +770,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
             if (!h->gvalid) {
                 for (auto& set : h->gexec) for (auto& g : set) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
                 h->gvalid = true;
-                h->gstale[0] = h->gstale[1] = false;
+                for (auto& f : h->gstale) f = false;
             }
             if (h->gstale[fam]) {                  // this family's key changed: its two sets go, the other family's stay
                 for (int f = 2 * fam; f < 2 * fam + 2; ++f) for (auto& g : h->gexec[f]) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -763,6 +790,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
                     e2 = hipGraphInstantiate(&gexec[bucket], g, nullptr, nullptr, 0);
                     (void)hipGraphDestroy(g);
                     if (e2 != hipSuccess) return rq_fail(RQAMD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
+                    ++h->n_capture;
                 } else {
                     // capture unavailable (e.g. the legacy default stream): eager launches, ~10x the launch count.
                     // Said once, loudly -- this is a performance cliff, not an error.
@@ -784,12 +812,15 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
     return RQAMD_OK;
 }
 
-// rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided behind their argument checks.  `guided`: `batch` images run as
+// host arrays of rqamd_rqt_sample_rows (batch rows each; top_k / top_p batch * D)
+struct RowParams { const float* temperature; const int* top_k; const float* top_p; const float* gscale; const uint64_t* seeds; };
+
+// rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
 // 2 * batch engine rows (rows batch.. conditioned on `uncond`), drawn from the guided logits with scale `gscale`
 static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active, const int64_t* cond, int batch,
                        const float* const* codebooks, int start_idx, float temperature, const int* top_k, const float* top_p,
                        uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream,
-                       bool guided = false, const int64_t* uncond = nullptr, float gscale = 1.f) {
+                       bool guided = false, const int64_t* uncond = nullptr, float gscale = 1.f, const RowParams* rp = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     h->step_on = false;
     const int rows = guided ? 2 * batch : batch;
@@ -797,12 +828,38 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     StepCtx c{};
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
     c.guided = guided; c.Bs = batch; c.gscale = gscale;
+    if (rp) {
+        // per-row values: host arrays -> one staging block owned by the handle -> h->row_* by asynchronous copies ahead of the position
+        // loop on the same stream, outside any capture.  The caller's arrays are read before this function returns; the staging block
+        // is what the copies read, so it is rewritten only once the stream has drained (idle already in the usual case: callers wait
+        // for the codes of one call before they make the next).
+        c.per_row = true; c.row_seeds = rp->seeds != nullptr;
+        const size_t nB = (size_t)batch, nD = nB * h->D;
+        const size_t oT = 0, oG = oT + nB * 4, oK = oG + nB * 4, oP = oK + nD * 4, oS = (oP + nD * 4 + 7) & ~(size_t)7, total = oS + nB * 8;
+        RQ_HIP(hipStreamSynchronize(st));
+        h->row_host.resize(total);
+        char* hb = h->row_host.data();
+        memcpy(hb + oT, rp->temperature, nB * 4);
+        if (guided) memcpy(hb + oG, rp->gscale, nB * 4);
+        memcpy(hb + oK, rp->top_k, nD * 4);
+        memcpy(hb + oP, rp->top_p, nD * 4);
+        if (rp->seeds) memcpy(hb + oS, rp->seeds, nB * 8);
+        RQ_HIP(hipMemcpyAsync(h->row_T, hb + oT, nB * 4, hipMemcpyHostToDevice, st));
+        if (guided) RQ_HIP(hipMemcpyAsync(h->row_gs, hb + oG, nB * 4, hipMemcpyHostToDevice, st));
+        RQ_HIP(hipMemcpyAsync(h->row_tk, hb + oK, nD * 4, hipMemcpyHostToDevice, st));
+        RQ_HIP(hipMemcpyAsync(h->row_tp, hb + oP, nD * 4, hipMemcpyHostToDevice, st));
+        if (rp->seeds) RQ_HIP(hipMemcpyAsync(h->row_seed, hb + oS, nB * 8, hipMemcpyHostToDevice, st));
+    }
     // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
     // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
     rqamd_rqt::Key k{};
-    k.B = rows; k.T = temperature; k.gs = guided ? gscale : 0.f; k.guided = guided ? 1 : 0; k.stream = stream;
-    for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; k.cb[d] = codebooks[d]; }
-    const int fam = guided ? 1 : 0;
+    k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream;
+    for (int d = 0; d < h->D; ++d) k.cb[d] = codebooks[d];
+    if (!rp) {             // (per-row calls: no parameter value is in a captured launch, so none is in the key)
+        k.T = temperature; k.gs = guided ? gscale : 0.f;
+        for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
+    }
+    const int fam = (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
     if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
@@ -873,6 +930,40 @@ extern "C" int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, con
     if (start_idx < 0) start_idx = 0;
     return sample_impl(h, partial, keep, keep ? pos_active_host : nullptr, cond, batch, codebooks, start_idx, temperature, top_k, top_p, seed,
                        offset, use_graph, codes_out, stream, true, uncond, guidance_scale);
+}
+
+// Per-row form (include/rqamd.h): plain, masked and guided sampling with a temperature, top-k, top-p, guidance scale and optionally a
+// Philox seed per image.  The launch sequence is that of the scalar forms with the per-row sampler kernels (rqt_sample_rows.hip) in
+// place of the scalar ones; row b is drawn exactly as the scalar form with b's values draws it.
+extern "C" int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep, const uint8_t* pos_active_host,
+                                     const int64_t* cond, const int64_t* uncond, int batch, const float* const* codebooks,
+                                     int start_h, int start_w, const float* temperature, const int* top_k, const float* top_p,
+                                     const float* guidance_scale, const uint64_t* seeds, uint64_t seed, uint64_t offset,
+                                     int use_graph, int64_t* codes_out, void* stream) {
+    if (!h || !partial || !codebooks || !temperature || !top_k || !top_p || !codes_out)
+        return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: null argument");
+    if (batch < 1 || batch > 0x3fffffff) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: batch < 1 (or 2 * batch overflows)");
+    if (uncond && !guidance_scale) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: uncond without guidance_scale (null)");
+    const bool guided = guidance_scale != nullptr;
+    for (int b = 0; b < batch; ++b) {
+        const float t = temperature[b];
+        if (!(t > 0.f) || !(t - t == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: temperature[%d] must be > 0 and finite", b);
+        if (guided && !(guidance_scale[b] - guidance_scale[b] == 0.f))
+            return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: guidance_scale[%d] must be finite", b);
+    }
+    int start_idx = start_h * h->cfg.W + start_w;
+    if (start_idx < 0) start_idx = 0;
+    const RowParams rp{temperature, top_k, top_p, guidance_scale, seeds};
+    static const int no_k[8] = {};
+    static const float no_p[8] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
+    return sample_impl(h, partial, keep, keep ? pos_active_host : nullptr, cond, batch, codebooks, start_idx, 1.f, no_k, no_p, seed, offset,
+                       use_graph, codes_out, stream, guided, uncond, 1.f, &rp);
+}
+
+extern "C" int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures) {
+    if (!h || !captures) return rq_fail(RQAMD_ERR_INVALID, "rqt_graph_captures: null argument");
+    *captures = h->n_capture;
+    return RQAMD_OK;
 }
 
 extern "C" int rqamd_rqt_logits(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,

@@ -92,6 +92,15 @@ struct SampleArgs {
     const float* logits_u;  // [rows][V] logits of the unconditional twins, or null: unguided
     float gscale;           // guidance scale s: g = c + (s - 1) (c - u)
     long out_mirror;        // != 0: the drawn code is also written to out[(row * out_stride + slot) + out_mirror] (the twin's slot); 0: none
+    // per-row parameters (rqamd_sample_logits_rows / rqamd_rqt_sample_rows): row_temperature non-null selects the per-row kernels
+    // (rqt_sample_rows.hip), which read the scalars above from these device arrays instead -- row r is drawn exactly as a scalar call with
+    // r's values draws it.  row_top_k / row_top_p are read at [row * D + d] and are required with row_temperature.
+    const float* row_temperature;   // [rows], or null: the scalar kernels
+    const int* row_top_k;           // [rows * D]
+    const float* row_top_p;         // [rows * D]
+    const float* row_gscale;        // [rows], or null: gscale above for every row
+    const uint64_t* row_seeds;      // [rows], or null: rng / seed above.  Non-null: row r draws with key row_seeds[r], Philox row field 0
+                                    // and counter offset + slot (rng is ignored) -- the stream of row 0 of a call seeded with row_seeds[r]
 };
 
 int rq_launch_guide_logits(const float* c, const float* u, int rows, int V, float scale, float* out, hipStream_t s);

@@ -16,8 +16,12 @@ static __device__ __forceinline__ float rq_u01(uint32_t r) { return fmaf((float)
 // rqt_sample_guided.hip compiles this file once more with RQ_SAMPLE_GUIDED_TU defined: only the sampler templates below and their
 // guided instantiations.  The guided kernels live in an object of their own because instantiating them next to the unguided ones
 // changes the code the compiler emits for sample_topk_kernel<false> (a module-level effect: register allocation of its top-k search),
-// and the unguided instruction stream is to stay as it is.
-#ifndef RQ_SAMPLE_GUIDED_TU
+// and the unguided instruction stream is to stay as it is.  rqt_sample_rows.hip does the same with RQ_SAMPLE_ROWS_TU for the per-row
+// instantiations (ROWS = true, unguided and guided), for the same reason.
+#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU)
+#define RQ_SAMPLE_ONLY_TU 1
+#endif
+#ifndef RQ_SAMPLE_ONLY_TU
 
 template <int NS>
 __global__ __launch_bounds__(256) void resid_ln_kernel(ResidLnArgs p) {
@@ -1355,7 +1359,7 @@ int rq_launch_add_int(int* p, int v, hipStream_t s) {
     return rq_check_launch("add_int_kernel");
 }
 
-#endif  // !RQ_SAMPLE_GUIDED_TU
+#endif  // !RQ_SAMPLE_ONLY_TU
 
 // =================================================================================================
 // on-device sampler: temperature, top-k, NaN scrub, softmax, top-p, renormalise, one draw per row
@@ -1459,6 +1463,32 @@ static __device__ __forceinline__ float guide_logit(float c, float u, float s) {
     return c == -__int_as_float(0x7f800000) ? c : fmaf(s - 1.0f, c - u, c);
 }
 
+// Per-row parameters (ROWS = true, rqt_sample_rows.hip): the launcher runs the three kernels over all rows, and a workgroup goes on
+// only if its row's class is the kernel's own -- the choice launch_sample makes from the scalars, made per row from the row's values:
+//   SMP_ROW_GUMBEL   no filter in effect, a draw wanted and no probs_out
+//   SMP_ROW_TOPK     0 < top_k < V, V <= 16384, V % 4 == 0 and a redo workspace: the register kernel, which may hand the row back
+//   SMP_ROW_GENERAL  everything else; the general kernel also takes the SMP_ROW_TOPK rows whose redo flag is set
+// The class decides arithmetic as well as speed (x * (1 / T) against x / T, the exponential race against Gumbel-max), so it is what
+// makes row r of a per-row call bit-identical to row r of a scalar call with r's values.  All loads here are uniform over the
+// workgroup (addresses depend on blockIdx alone).
+enum { SMP_ROW_GUMBEL = 0, SMP_ROW_TOPK = 1, SMP_ROW_GENERAL = 2 };
+static __device__ __forceinline__ int sample_row_class(const SampleArgs& p, int row) {
+    const int k = p.row_top_k[(long)row * p.D + p.d];
+    const float tp = p.row_top_p[(long)row * p.D + p.d];
+    const bool k_on = k > 0 && k < p.V;
+    if (!k_on && (tp < 0.f || tp >= 1.0f) && !p.probs_out && p.out) return SMP_ROW_GUMBEL;
+    if (k_on && p.V <= SMP_T * SMP_VPT && p.V % 4 == 0 && p.redo) return SMP_ROW_TOPK;
+    return SMP_ROW_GENERAL;
+}
+// the row's own values into the kernel's copy of the arguments: from here on the scalar code runs unchanged
+static __device__ __forceinline__ void sample_row_params(SampleArgs& p, int row) {
+    p.temperature = p.row_temperature[row];
+    p.top_k = p.row_top_k[(long)row * p.D + p.d];
+    p.top_p = p.row_top_p[(long)row * p.D + p.d];
+    if (p.row_gscale) p.gscale = p.row_gscale[row];
+    if (p.row_seeds) { p.rng = nullptr; p.seed = p.row_seeds[row]; }      // (p.offset stays: 0 in the engine, the caller's elsewhere)
+}
+
 // The three samplers are templates on GUIDED.  <false>: the unguided kernels, whose instruction stream the parameter leaves as it was.
 // <true>: the row of p.logits_u is loaded next to the row of p.logits, the same way, and the two are mixed through guide_logit();
 // the drawn code also goes to the twin's slot (p.out_mirror).
@@ -1469,7 +1499,7 @@ static __device__ __forceinline__ void sample_store(const SampleArgs& p, int row
     if (GUIDED && p.out_mirror) p.out[o + p.out_mirror] = (int64_t)code;
 }
 
-template <bool GUIDED>
+template <bool GUIDED, bool ROWS = false>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1480,7 +1510,13 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     unsigned* bcast = hist + 256;              // [4]
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
-    if (p.redo && !p.redo[row]) return;        // second pass after sample_topk_kernel: only the rows it handed back
+    if (ROWS) {                                // the general rows, and the register kernel's rows that it handed back
+        const int cls = sample_row_class(p, row);
+        if (cls == SMP_ROW_GUMBEL || (cls == SMP_ROW_TOPK && !p.redo[row])) return;
+        sample_row_params(p, row);
+    }
+    if (!ROWS && p.redo && !p.redo[row]) return;        // second pass after sample_topk_kernel: only the rows it handed back
+    const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     const float* lg = p.logits + (long)row * V;
     const float NEG_INF = -__int_as_float(0x7f800000);
 
@@ -1619,7 +1655,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     int besti = 0x7fffffff;
     for (int i4 = tid; i4 * 4 < V; i4 += SMP_T) {
         unsigned r[4];
-        philox4x32_10((unsigned)i4, (unsigned)row, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+        philox4x32_10((unsigned)i4, (unsigned)prow, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int i = i4 * 4 + e;
@@ -1692,7 +1728,7 @@ static __device__ __forceinline__ int blk_count_pp(int wave_cnt, SmpShared& sh, 
 }
 
 // softmax -> top-p -> renormalise -> (probs_out) -> draw, on NV scaled logits per thread (absent entries: idx < 0)
-template <bool GUIDED, int NV, typename IdxF>
+template <bool GUIDED, bool ROWS, int NV, typename IdxF>
 static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&q)[NV], IdxF idx_of, int row, SmpShared& sh) {
     const int tid = threadIdx.x, V = p.V;
     const float NEG_INF = -__int_as_float(0x7f800000);
@@ -1789,6 +1825,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
     const int slot = p.pos ? (*p.pos) * p.D + p.d : 0;
     const uint64_t seed = p.rng ? p.rng[0] : p.seed;
     const uint64_t off = (p.rng ? p.rng[1] : p.offset) + (uint64_t)slot;
+    const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     float best = -1.f;
     int besti = 0x7fffffff;
 #pragma unroll
@@ -1796,7 +1833,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
         const int i = idx_of(k);
         if (i < 0) continue;
         unsigned r[4];
-        philox4x32_10((unsigned)(i >> 2), (unsigned)row, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+        philox4x32_10((unsigned)(i >> 2), (unsigned)prow, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
         const unsigned w = (i & 3) == 0 ? r[0] : (i & 3) == 1 ? r[1] : (i & 3) == 2 ? r[2] : r[3];
         const float u = rq_u01(w);
         const float sc = q[k] / (-logf(u));
@@ -1819,11 +1856,15 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
     }
 }
 
-template <bool GUIDED>
+template <bool GUIDED, bool ROWS = false>
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given (redo[row] is neither written nor read)
+    if (ROWS) {                                // rows of another class leave redo[row] alone: the general kernel reads it for this class only
+        if (sample_row_class(p, row) != SMP_ROW_TOPK) return;
+        sample_row_params(p, row);
+    }
     const float* lg = p.logits + (long)row * V;
     const int V4 = V >> 2;
     // thread t owns float4 groups t, t+256, ...: value 4j+e is vocabulary index (t + 256 j) * 4 + e
@@ -1940,7 +1981,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
         qi[k] = s < total ? sh.idx[s] : -1;
     }
     rq_syncthreads();
-    sample_tail<GUIDED, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
+    sample_tail<GUIDED, ROWS, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
 }
 
 // Unfiltered draw (top_k covers the vocabulary, top_p >= 1: the reference's defaults, transformers.py:309-323):
@@ -1948,12 +1989,17 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
 // Gumbel_i = -log(-log u_i) from the same Philox counters as sample_kernel -- no max / sum reductions, no
 // LDS copy of the row, so occupancy is set by registers only (the general kernel holds V floats in LDS:
 // 2 workgroups per CU, 830 us per call at 4096 x 16384; this one is bound by reading the logits once).
-template <bool GUIDED>
+template <bool GUIDED, bool ROWS = false>
 __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
+    if (ROWS) {
+        if (sample_row_class(p, row) != SMP_ROW_GUMBEL) return;
+        sample_row_params(p, row);
+    }
+    const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     const float* lg = p.logits + (long)row * V;
     const float inv_t = 1.0f / p.temperature;
     const int slot = p.pos ? (*p.pos) * p.D + p.d : 0;
@@ -1986,7 +2032,7 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
             for (int e = 0; e < 4; ++e) v[e] = guide_logit(v[e], w[e], p.gscale);
         }
         unsigned r[4];
-        philox4x32_10((unsigned)i4, (unsigned)row, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+        philox4x32_10((unsigned)i4, (unsigned)prow, (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int i = i4 * 4 + e;
@@ -2043,11 +2089,47 @@ static int launch_sample(const SampleArgs& a, hipStream_t s) {
     return rq_check_launch("sample_kernel");
 }
 
-#ifdef RQ_SAMPLE_GUIDED_TU
+#ifdef RQ_SAMPLE_ROWS_TU
+// per-row parameters: the three kernels over all rows, each workgroup leaving at once unless the row is of its class (sample_row_class).
+// The streaming kernel cannot write probs_out and the register kernel needs V <= 16384, V % 4 == 0 and the redo workspace: where a
+// kernel can have no rows it is not launched.  The general kernel comes last (it reads the flags the register kernel wrote).  The
+// values are device arrays, so nothing about them is checked here; the kernels trap on none (temperature <= 0 or NaN draws garbage).
+template <bool GUIDED>
+static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
+    if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
+    if (!a.row_top_k || !a.row_top_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: per-row top_k / top_p missing");
+    SampleArgs b = a;
+    static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch, as in launch_sample
+    if (env_lds_only) b.redo = nullptr;
+    if (!b.probs_out && b.out) {
+        const auto kern = sample_gumbel_kernel<GUIDED, true>;
+        RQ_LAUNCH(kern, dim3(b.rows), dim3(256), 0, s, b);
+        RQ_TRY(rq_check_launch("sample_gumbel_kernel (per row)"));
+    }
+    if (b.V <= SMP_T * SMP_VPT && b.V % 4 == 0 && b.redo) {
+        const auto kern = sample_topk_kernel<GUIDED, true>;
+        RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), 0, s, b);
+        RQ_TRY(rq_check_launch("sample_topk_kernel (per row)"));
+    }
+    const size_t smem = (size_t)b.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
+    const auto kern = sample_kernel<GUIDED, true>;
+    static RqDeviceOnce attr_once;      // kernel attributes are per device
+    if (attr_once.first()) {
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    }
+    RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), smem, s, b);
+    return rq_check_launch("sample_kernel (per row)");
+}
+int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
+    return a.logits_u ? launch_sample_per_row<true>(a, s) : launch_sample_per_row<false>(a, s);
+}
+#elif defined(RQ_SAMPLE_GUIDED_TU)
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s) { return launch_sample<true>(a, s); }
 #else
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s);     // rqt_sample_guided.hip
+int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s);    // rqt_sample_rows.hip
 int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+    if (a.row_temperature) return rq_launch_sample_per_row(a, s);
     return a.logits_u ? rq_launch_sample_guided(a, s) : launch_sample<false>(a, s);
 }
 
@@ -2099,6 +2181,21 @@ extern "C" int rqamd_sample_logits(const float* logits, int rows, int vocab, flo
     a.logits = logits; a.rows = rows; a.V = vocab; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
     a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.probs_out = probs_out; a.D = 1;
     a.redo = row_flags;     // caller-owned (rows ints) or NULL: without it every row takes the general kernel
+    return rq_launch_sample(a, (hipStream_t)stream);
+}
+
+// per-row form: temperature / top_k / top_p (and seeds, or null) are device arrays of `rows` entries.  Nothing is kept on the library
+// side and nothing is read on the host: the caller validates temperature > 0
+extern "C" int rqamd_sample_logits_rows(const float* logits, int rows, int vocab, const float* temperature, const int* top_k,
+                                        const float* top_p, const uint64_t* seeds, uint64_t seed, uint64_t offset,
+                                        int64_t* samples_out, float* probs_out, int* row_flags, void* stream) {
+    if (!logits || rows < 0 || !temperature || !top_k || !top_p) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_rows: bad argument (null array or rows < 0)");
+    if (rows == 0) return RQAMD_OK;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = vocab; a.temperature = 1.0f; a.top_k = 0; a.top_p = -1.0f;
+    a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.probs_out = probs_out; a.D = 1;
+    a.redo = row_flags;
+    a.row_temperature = temperature; a.row_top_k = top_k; a.row_top_p = top_p; a.row_seeds = seeds;
     return rq_launch_sample(a, (hipStream_t)stream);
 }
 
@@ -2358,4 +2455,4 @@ int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
     RQ_LAUNCH(log_prob_kernel, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
     return rq_check_launch("log_prob_kernel");
 }
-#endif  // !RQ_SAMPLE_GUIDED_TU
+#endif  // !RQ_SAMPLE_ONLY_TU

@@ -63,6 +63,8 @@ _SIGS = {
                                  C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_sample_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_sample_logits_rows': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_vae_create': (C.c_int, [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]),
     'rqamd_vae_destroy': (C.c_int, [C.c_void_p]),
     'rqamd_vae_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
@@ -83,6 +85,11 @@ _SIGS = {
                                           C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int),
                                           C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_guide_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
+                                        C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward_onepass': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -338,6 +345,29 @@ def sample_logits(logits, temperature=1.0, top_k=None, top_p=None, seed=0, offse
                                         0 if top_k is None else int(top_k), -1.0 if top_p is None else float(top_p),
                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(samples), ptr(probs),
                                         ptr(flags), stream_of(logits)))
+    return samples, probs
+
+
+def sample_logits_rows(logits, temperature, top_k, top_p, seeds=None, seed=0, offset=0, want_probs=False, want_samples=True):
+    """rqamd_sample_logits_rows: sample_logits with one temperature, top_k and top_p per row.  logits (rows, vocab) fp32; temperature
+    (rows,) float32, top_k (rows,) int32 (<= 0 or >= vocab: off), top_p (rows,) float32 (< 0: off) and seeds (rows,) int64 or None are
+    tensors on the device of `logits`.  Row r comes out as row r of sample_logits(logits, temperature[r], top_k[r], top_p[r], seed,
+    offset); with seeds, as row 0 of sample_logits(logits[r:r+1], ..., seed=seeds[r], offset=0).  The values are not read on the host:
+    the caller validates temperature > 0."""
+    rows, vocab = logits.shape
+    for name, t, dt in (('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32), ('top_p', top_p, torch.float32),
+                        ('seeds', seeds, torch.int64)):
+        if t is None and name == 'seeds':
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (rows,) or t.dtype != dt or t.device != logits.device:
+            raise ValueError(f'sample_logits_rows: {name} must be a ({rows},) {dt} tensor on {logits.device}')
+    samples = torch.empty((rows,), dtype=torch.int64, device=logits.device) if want_samples else None
+    probs = torch.empty((rows, vocab), dtype=torch.float32, device=logits.device) if want_probs else None
+    flags = torch.empty((max(rows, 1),), dtype=torch.int32, device=logits.device)
+    with on_device_of(logits):
+        check(lib().rqamd_sample_logits_rows(ptr(logits, torch.float32), rows, vocab, ptr(temperature), ptr(top_k), ptr(top_p), ptr(seeds),
+                                             int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(samples), ptr(probs),
+                                             ptr(flags), stream_of(logits)))
     return samples, probs
 
 
@@ -682,6 +712,64 @@ class RqtEngine(_Engine):
                                                         float(temperature), float(guidance_scale), tk, tp, int(seed) & (2 ** 64 - 1),
                                                         int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
         return out
+
+    def sample_rows(self, partial, keep, pos_active, cond, uncond, codebooks, start_loc, temperature, top_k, top_p, guidance_scale,
+                    seeds, seed, offset, use_graph):
+        """rqamd_rqt_sample_rows: sampling parameters per image.  temperature (B,), top_k (B, D), top_p (B, D), guidance_scale (B,) or
+        None (with uncond None: unguided) and seeds (B,) or None are HOST sequences (nested for the two (B, D) tables); `keep` /
+        `pos_active` as in sample_masked or None, `uncond` as in sample_guided.  Image b is drawn as the scalar entry point draws row
+        b with b's values; with seeds, from Philox key seeds[b] whatever its place in the batch (seed / offset unused)."""
+        self._check(partial, cond, codebooks)
+        B = partial.shape[0]
+        c = self.cfg
+        D = c.D
+        if uncond is not None:
+            want = (B, max(c.block_size_cond, 1))
+            if tuple(uncond.shape) != want:
+                raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {want}')
+            self._on_my_device(uncond)
+            if guidance_scale is None:
+                raise ValueError('sample_rows: uncond needs guidance_scale')
+        T = [float(t) for t in temperature]
+        tk = [int(k) for row in top_k for k in row]
+        tp = [float(p) for row in top_p for p in row]
+        gs = None if guidance_scale is None else [float(s) for s in guidance_scale]
+        sd = None if seeds is None else [int(s) for s in seeds]
+        if len(T) != B or len(tk) != B * D or len(tp) != B * D or (gs is not None and len(gs) != B) or (sd is not None and len(sd) != B):
+            raise ValueError(f'sample_rows: per-image values of the wrong shape for {B} images of depth {D}')
+        if not all(math.isfinite(t) and t > 0 for t in T):
+            raise ValueError('sample_rows: every temperature must be > 0 and finite')
+        if gs is not None and not all(math.isfinite(s) for s in gs):
+            raise ValueError('sample_rows: every guidance_scale must be finite')
+        if sd is not None and any(s < 0 or s >= 2 ** 64 for s in sd):
+            raise ValueError('sample_rows: seeds must be in 0 .. 2**64 - 1')
+        kp = None
+        if keep is not None:
+            if keep.dtype != torch.uint8 or tuple(keep.shape) != tuple(partial.shape):
+                raise ValueError(f'keep of shape {tuple(keep.shape)} / {keep.dtype}; expected {tuple(partial.shape)} / torch.uint8')
+            self._on_my_device(keep)
+            kp = ptr(keep, torch.uint8)
+        pa = None
+        if pos_active is not None:
+            if len(pos_active) != c.H * c.W:
+                raise ValueError(f'pos_active has {len(pos_active)} entries; expected {c.H * c.W}')
+            pa = (C.c_uint8 * (c.H * c.W))(*[1 if a else 0 for a in pos_active])
+        out = torch.empty_like(partial)
+        cbs = _ptr_array(codebooks[:D])
+        aT, ak, ap = (C.c_float * B)(*T), (C.c_int * (B * D))(*tk), (C.c_float * (B * D))(*tp)
+        ag = None if gs is None else (C.c_float * B)(*gs)
+        asd = None if sd is None else (C.c_uint64 * B)(*sd)
+        self._run(lambda: self._L.rqamd_rqt_sample_rows(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64),
+                                                      ptr(uncond, torch.int64), B, cbs, int(start_loc[0]), int(start_loc[1]), aT, ak, ap,
+                                                      ag, asd, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                                      int(bool(use_graph)), ptr(out), stream_of(partial)))
+        return out
+
+    def graph_captures(self):
+        """position graphs this handle has captured so far (rqamd_rqt_graph_captures); a call that only replays leaves it unchanged"""
+        n = C.c_int64()
+        check(self._L.rqamd_rqt_graph_captures(self._h, C.byref(n)), self._L)
+        return n.value
 
     def logits(self, codes, cond, codebooks):
         self._check(codes, cond, codebooks)

@@ -12,6 +12,7 @@ softmax / logits are fp32 either way.  Arguments of ``sample`` that cannot mean 
 are never ignored silently: ``cached=False`` runs a real uncached loop (every step recomputes all logits; the reference's own
 cross-check of its cache, transformers.py:352-356); ``is_tqdm`` / ``desc`` have nothing to report on (the
 whole loop is one asynchronous C call) and ``fast`` is unused by the reference itself."""
+import contextlib
 import math
 import os
 from collections import OrderedDict
@@ -101,6 +102,7 @@ class RQTransformer(Stage2Model):
         # launch; 'one_pass' (or RQAMD_FORWARD=one_pass): every position at once, no KV cache (rqamd_rqt_forward_onepass) -- same
         # arithmetic, other GEMM tiles.  cached_forward and sample (cached or not) always step.
         self.forward_mode = os.environ.get('RQAMD_FORWARD', 'stepped')
+        self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -303,10 +305,18 @@ class RQTransformer(Stage2Model):
         to every image.  A kept code stays as given and conditions everything drawn after it; every other code is drawn exactly as
         the unmasked call draws it (same logits, filter and Philox counter), whatever `partial_sample` holds there.  Positions before
         `start_loc` are kept in addition.  Inpainting, outpainting, depth refinement and a region per image are masks; None: the
-        reference's behaviour."""
+        reference's behaviour.
+        Per-image parameters (not in the reference): ``temperature`` as a (B,) tensor, ``top_k`` / ``top_p`` as (B,) or (B, D) tensors
+        give every image its own values (numbers and lists keep the reference's meaning: one value, or one per depth, for every
+        image; arguments not given as tensors are broadcast).  Image b is drawn exactly as a call with b's values as scalars draws
+        row b, whatever the other images ask for, and one set of captured graphs serves every setting.  Inside ``with
+        self.seeds(s)`` image b draws from the Philox stream of seed s[b] instead of the device generator (see seeds())."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p)
+        if rows is not None:
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask)
         top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
@@ -356,6 +366,143 @@ class RQTransformer(Stage2Model):
             top_p_list = [min(top_p[i], 1.0) for i in range(D)]
         return top_k_list, top_p_list
 
+    # ------------------------------------------------------------------ per-image sampling parameters
+    @contextlib.contextmanager
+    def seeds(self, seeds):
+        """Per-image Philox seeds for the sample() / sample_guided() calls made inside the block: ``seeds`` is a (B,) integer tensor
+        or a sequence of B non-negative integers.  Image b is then drawn from the stream of row 0 of a call made after
+        ``torch.manual_seed(seeds[b])`` -- whatever its place in the batch and whatever the other images are -- and the device
+        generator is not consumed.  (A context rather than an argument: the argument lists of sample() and sample_guided() are the
+        reference's plus keep_mask / uncond / guidance_scale, and stay so.)  ``sampler='torch'`` has no per-row key and raises."""
+        if torch.is_tensor(seeds):
+            if seeds.dtype.is_floating_point or seeds.dtype.is_complex or seeds.dtype == torch.bool or seeds.dim() != 1:
+                raise ValueError(f'seeds of shape {tuple(seeds.shape)} / {seeds.dtype}; expected a (B,) integer tensor')
+            vals = [int(v) for v in seeds.tolist()]
+        else:
+            vals = list(seeds)
+            if not all(isinstance(v, int) and not isinstance(v, bool) for v in vals):
+                raise ValueError('seeds must be integers')
+        if any(v < 0 or v >= 2 ** 64 for v in vals):
+            raise ValueError('seeds must be in 0 .. 2**64 - 1 (negative seeds are refused)')
+        saved, self._image_seeds = self._image_seeds, vals
+        try:
+            yield self
+        finally:
+            self._image_seeds = saved
+
+    def _per_image(self, B, temperature, top_k, top_p, guidance_scale=None):
+        """None when no argument is per image (no tensor of one or more dimensions, no seeds(): the scalar entry points, untouched), else
+        the per-image tables on the host, validated: T [B], tk / tp [B][D] (clipped like _filter_lists: top_k to vocab_size[d], top_p
+        to 1.0), gs [B] or None, seeds [B] or None"""
+        def per(a):
+            return torch.is_tensor(a) and a.dim() >= 1
+        if not (per(temperature) or per(top_k) or per(top_p) or per(guidance_scale) or self._image_seeds is not None):
+            return None
+        D = self.block_size[2]
+
+        def vec(a, name, default):
+            if per(a):
+                if tuple(a.shape) != (B,):
+                    raise ValueError(f'{name} of shape {tuple(a.shape)}; expected ({B},) (one value per image)')
+                if a.dtype.is_complex or a.dtype == torch.bool:
+                    raise ValueError(f'{name} of dtype {a.dtype}; expected a real tensor')
+                return [float(v) for v in a.to(torch.float32).tolist()]
+            return [float(default if a is None else a)] * B
+
+        def table(a, name, integer):
+            if a.dim() not in (1, 2) or a.shape[0] != B or (a.dim() == 2 and a.shape[1] != D):
+                raise ValueError(f'{name} of shape {tuple(a.shape)}; expected ({B},) or ({B}, {D})')
+            if integer and (a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool):
+                raise ValueError(f'{name} of dtype {a.dtype}; expected an integer tensor')
+            if not integer and not a.dtype.is_floating_point:
+                raise ValueError(f'{name} of dtype {a.dtype}; expected a floating-point tensor')
+            a = a if a.dim() == 2 else a[:, None].expand(B, D)
+            return (a if integer else a.to(torch.float32)).tolist()
+        top_k_list, top_p_list = self._filter_lists(None if per(top_k) else top_k, None if per(top_p) else top_p)
+        tk = [list(top_k_list) for _ in range(B)]
+        tp = [list(top_p_list) for _ in range(B)]
+        if per(top_k):
+            tk = [[min(int(k), self.vocab_size[d]) for d, k in enumerate(row)] for row in table(top_k, 'top_k', True)]
+        if per(top_p):
+            tp = [[min(float(p), 1.0) for p in row] for row in table(top_p, 'top_p', False)]
+            if any(p != p for row in tp for p in row):
+                raise ValueError('top_p holds NaN')
+        T = vec(temperature, 'temperature', 1.0)
+        if not all(math.isfinite(t) and t > 0 for t in T):
+            raise ValueError('every temperature must be > 0 and finite')
+        gs = None
+        if guidance_scale is not None:
+            gs = vec(guidance_scale, 'guidance_scale', 1.0)
+            if not all(math.isfinite(s) for s in gs):
+                raise ValueError('every guidance_scale must be finite')
+        sd = self._image_seeds
+        if sd is not None and len(sd) != B:
+            raise ValueError(f'seeds of shape ({len(sd)},); expected ({B},) (one seed per image)')
+        return dict(T=T, tk=tk, tp=tp, gs=gs, seeds=sd)
+
+    def _rows_on_device(self, rows, device):
+        """the tables of _per_image as the device tensors _native.sample_logits_rows takes (host loops): T (B,), tk / tp one (B,) per depth"""
+        D = self.block_size[2]
+        dev = dict(rows)
+        dev['T_dev'] = torch.tensor(rows['T'], dtype=torch.float32, device=device)
+        dev['tk_dev'] = [torch.tensor([r[d] for r in rows['tk']], dtype=torch.int32, device=device) for d in range(D)]
+        dev['tp_dev'] = [torch.tensor([r[d] for r in rows['tp']], dtype=torch.float32, device=device) for d in range(D)]
+        sd = rows['seeds']
+        dev['seeds_dev'] = None if sd is None else torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in sd], dtype=torch.int64, device=device)
+        return dev
+
+    @staticmethod
+    def _guide_rows(c, u, scales):
+        """guide_logits with one scale per row: the rows of each distinct scale through the scalar entry point (elementwise, so row b
+        is what the engine's guided sampler mixes for b)"""
+        out = torch.empty_like(c)
+        for s in sorted(set(scales)):
+            idx = torch.tensor([i for i, v in enumerate(scales) if v == s], dtype=torch.long, device=c.device)
+            out[idx] = _native.guide_logits(c[idx].contiguous(), u[idx].contiguous(), s)
+        return out
+
+    def _sample_per_image(self, rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, guided=False, uncond=None):
+        """sample() / sample_guided() with per-image parameters: rqamd_rqt_sample_rows, or the two host loops over sample_logits_rows"""
+        (H, W, D) = self.block_size
+        B = partial_sample.shape[0]
+        device = partial_sample.device
+        if guided and uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
+            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+        if rows['seeds'] is not None and self.sampler == 'torch':
+            raise ValueError("sampler='torch' draws with torch.multinomial from the device generator, which has no per-row key: seeds() is "
+                             'available with the default sampler')
+        if self.sampler == 'torch' and not cached:
+            raise NotImplementedError("sampler='torch' steps the cached engine; cached=False is available with the default sampler")
+        eng = self._eng(amp)
+        cbs = self._checked_codebooks(model_aux)
+        xs = partial_sample.to(torch.long).contiguous()
+        c = self._cond(cond, B, device)
+        u = self._cond(uncond, B, device) if guided else None
+        keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
+        if self.sampler == 'torch' or not cached:
+            if keep is not None:
+                xs = torch.where(keep, xs, torch.zeros_like(xs))            # (see sample(): the host loops embed every code)
+            xs2, c2, scale = xs, c, None
+            if guided:
+                xs2, scale = torch.cat([xs, xs]), rows['gs']
+                if c is not None or u is not None:
+                    zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
+                    c2 = torch.cat([zeros if c is None else c, zeros if u is None else u])
+            dev = self._rows_on_device(rows, device)
+            if self.sampler == 'torch':
+                return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, None, None, None, keep, active, scale, rows=dev)
+            seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
+            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, None, None, None, seed, offset, keep, active, scale, rows=dev)
+        seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
+        keep8, pos_active, start = None, None, start_loc
+        if keep is not None:
+            keep8 = keep.to(torch.uint8).contiguous()
+            pos_active = [bool(a) for a in active.any(dim=1).tolist()]
+            start = (0, 0)                                                   # (the kept prefix is part of `keep`)
+        return self._on_side_stream(device, lambda: eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'],
+                                                                    rows['gs'] if guided else None, rows['seeds'], seed, offset,
+                                                                    self.use_graph))
+
     @torch.no_grad()
     def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                       amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, uncond=None, guidance_scale=1.0,
@@ -366,10 +513,14 @@ class RQTransformer(Stage2Model):
         inside the engine over 2B rows (rqamd_rqt_sample_guided): the unconditional twin of an image sees exactly the codes its
         conditional twin drew, and row b uses the temperature, top-k, top-p and Philox counter of row b of sample().  Returns
         (B,H,W,D) int64.  ``keep_mask`` composes as in sample(); ``cached=False`` and ``sampler='torch'`` are the host loops of
-        sample() over the 2B rows, the former bit for bit equal to ``cached=True``."""
+        sample() over the 2B rows, the former bit for bit equal to ``cached=True``.  Per-image ``temperature`` / ``top_k`` / ``top_p``
+        tensors and ``with self.seeds(...)`` as in sample(); ``guidance_scale`` as a (B,) tensor gives every image its own scale."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, guidance_scale)
+        if rows is not None:
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, True, uncond)
         if not math.isfinite(float(guidance_scale)):
             raise ValueError(f'guidance_scale {guidance_scale} is not finite')
         scale = float(guidance_scale)
@@ -440,7 +591,7 @@ class RQTransformer(Stage2Model):
         return keep, host[:-1].view(H * W, D)
 
     def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None,
-                         guidance_scale=None):
+                         guidance_scale=None, rows=None):
         """``cached=False`` (transformers.py:352-356): nothing is carried from one step to the next -- every step recomputes the
         logits of the whole code map from the codes drawn so far (one teacher-forced pass of the engine per step, 256 per
         batch, as slow as the reference's own uncached loop) and samples position (h, w, d) from them with the draw the
@@ -450,7 +601,9 @@ class RQTransformer(Stage2Model):
         pass -- so both pick the same kernels for a given B)
         ``guidance_scale`` (sample_guided): `xs` / `cond` hold 2B rows, images then their unconditional twins; each step draws B rows
         from guide_logits of the two halves -- Philox row b, as the engine's guided sampler -- and writes the code to both halves;
-        `keep` has B rows and the first B rows are returned."""
+        `keep` has B rows and the first B rows are returned.
+        ``rows`` (per-image parameters, _rows_on_device): the draw is sample_logits_rows with the tables of the rows -- and
+        guidance_scale a list, one scale per image -- in place of the scalars; with seeds, key seeds[b] and counter pos * D + d."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
@@ -464,24 +617,32 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(xs.device, lambda: eng.logits(xs, cond, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
-                if guidance_scale is not None:
+                if guidance_scale is not None and rows is not None:
+                    logits = self._guide_rows(logits[:n], logits[n:], guidance_scale)
+                elif guidance_scale is not None:
                     logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
-                idx, _ = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], seed=seed,
-                                               offset=offset + pos * D + d)
+                if rows is not None:
+                    idx, _ = _native.sample_logits_rows(logits, rows['T_dev'], rows['tk_dev'][d], rows['tp_dev'][d], seeds=rows['seeds_dev'],
+                                                        seed=seed, offset=offset + pos * D + d)
+                else:
+                    idx, _ = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], seed=seed,
+                                                   offset=offset + pos * D + d)
                 if keep is not None:
                     idx = torch.where(keep[:, h, w, d], xs[:n, h, w, d], idx)
                 xs[:, h, w, d] = idx if guidance_scale is None else torch.cat([idx, idx])
         return xs if guidance_scale is None else xs[:n].contiguous()
 
     def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, keep=None, active=None,
-                                  guidance_scale=None):
+                                  guidance_scale=None, rows=None):
         """``self.sampler = 'torch'`` (or RQAMD_SAMPLER=torch): the loop of transformers.py:346-364 driven from the host, one engine
         step per (h, w, d), the draw by ``torch.multinomial(probs, num_samples=1)`` on the filtered probabilities -- the call
         sample_from_logits makes (rqvae/utils/utils.py:112), so the device generator is consumed exactly as the reference consumes
         it (one multinomial over a (B, V) tensor per step).  ~10x slower than the default on-device sampler (no graphs, one host
         round per step); meant for seed-for-seed comparisons, not for throughput.
         ``guidance_scale`` (sample_guided): 2B rows are stepped, images then their unconditional twins; the B draws of a step come
-        from guide_logits of the two halves and are set in both; `keep` has B rows and the first B rows are returned."""
+        from guide_logits of the two halves and are set in both; `keep` has B rows and the first B rows are returned.
+        ``rows`` (per-image parameters, _rows_on_device): the probabilities come from sample_logits_rows, every row filtered with its
+        own values (and guidance_scale is a list, one scale per image)."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
@@ -500,9 +661,15 @@ class RQTransformer(Stage2Model):
                 logits = eng.step_logits(pos, d)
                 if active is not None and not active[pos, d]:
                     continue                           # given in every row: no draw (the step fed the head stack's KV cache)
-                if guidance_scale is not None:
+                if guidance_scale is not None and rows is not None:
+                    logits = self._guide_rows(logits[:n], logits[n:], guidance_scale)
+                elif guidance_scale is not None:
                     logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
-                _, probs = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], want_probs=True, want_samples=False)
+                if rows is not None:
+                    _, probs = _native.sample_logits_rows(logits.contiguous(), rows['T_dev'], rows['tk_dev'][d], rows['tp_dev'][d],
+                                                          want_probs=True, want_samples=False)
+                else:
+                    _, probs = _native.sample_logits(logits, temperature, top_k_list[d], top_p_list[d], want_probs=True, want_samples=False)
                 try:
                     idx = torch.multinomial(probs, num_samples=1).squeeze(-1)
                 except RuntimeError:
