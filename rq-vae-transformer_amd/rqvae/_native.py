@@ -240,9 +240,19 @@ def rq_code_norms(codebook):
     return out
 
 
-def rq_quantize(x, codebooks, want_quants=True, norms=None):
+def _out_like(out, shape, dtype, device, name):
+    """the caller's output buffer (tests: a view into a guard-filled buffer) after a shape / dtype / device check, or a fresh one"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f'{name}: out must be a {tuple(shape)} {dtype} tensor on {device}')
+    return out
+
+
+def rq_quantize(x, codebooks, want_quants=True, norms=None, out=None):
     """x (n_vec, dim) fp32; codebooks: list of (K_i, dim) fp32 (padding row excluded); norms: list of rq_code_norms(cb)
-    (computed here when not given -- callers that quantise repeatedly cache them per codebook version).
+    (computed here when not given -- callers that quantise repeatedly cache them per codebook version); out: (codes, quant_cum)
+    buffers to write into (quant_cum None when not want_quants).
     -> codes (n_vec, depth) int64, quant_cum (depth, n_vec, dim) fp32 or None."""
     n_vec, dim = x.shape
     depth = len(codebooks)
@@ -256,8 +266,9 @@ def rq_quantize(x, codebooks, want_quants=True, norms=None):
             if key not in seen:
                 seen[key] = rq_code_norms(cb)
             norms.append(seen[key])
-    codes = torch.empty((n_vec, depth), dtype=torch.int64, device=x.device)
-    quants = torch.empty((depth, n_vec, dim), dtype=torch.float32, device=x.device) if want_quants else None
+    out_codes, out_quants = out if out is not None else (None, None)
+    codes = _out_like(out_codes, (n_vec, depth), torch.int64, x.device, 'rq_quantize codes')
+    quants = _out_like(out_quants, (depth, n_vec, dim), torch.float32, x.device, 'rq_quantize quant_cum') if want_quants else None
     ws = None
     if 0 < n_vec < 96 * 64:          # small inputs: scratch for the codebook-split path (residual + per-split partial minima)
         ws = torch.empty((n_vec * dim * 4 + n_vec * 64 * 8,), dtype=torch.uint8, device=x.device)
@@ -268,12 +279,14 @@ def rq_quantize(x, codebooks, want_quants=True, norms=None):
     return codes, quants
 
 
-def rq_soft_codes(x, codebooks, norms, temp=1.0, stochastic=False, seed=0, offset=0):
-    """x (n_vec, dim) fp32 -> (soft codes (n_vec, depth, K) fp32, codes (n_vec, depth) int64): RQBottleneck.get_soft_codes."""
+def rq_soft_codes(x, codebooks, norms, temp=1.0, stochastic=False, seed=0, offset=0, out=None):
+    """x (n_vec, dim) fp32 -> (soft codes (n_vec, depth, K) fp32, codes (n_vec, depth) int64): RQBottleneck.get_soft_codes.
+    out: (soft, codes) buffers to write into."""
     n_vec, dim = x.shape
     depth, K = len(codebooks), codebooks[0].shape[0]
-    soft = torch.empty((n_vec, depth, K), dtype=torch.float32, device=x.device)
-    codes = torch.empty((n_vec, depth), dtype=torch.int64, device=x.device)
+    out_soft, out_codes = out if out is not None else (None, None)
+    soft = _out_like(out_soft, (n_vec, depth, K), torch.float32, x.device, 'rq_soft_codes soft')
+    codes = _out_like(out_codes, (n_vec, depth), torch.int64, x.device, 'rq_soft_codes codes')
     ws = torch.empty((max(n_vec, 1) * (dim * 4 + 512 + K * 4),), dtype=torch.uint8, device=x.device)
     with on_device_of(x):
         check(lib().rqamd_rq_soft_codes(ptr(x, torch.float32), _ptr_array(codebooks), _ptr_array(norms),
@@ -283,12 +296,12 @@ def rq_soft_codes(x, codebooks, norms, temp=1.0, stochastic=False, seed=0, offse
     return soft, codes
 
 
-def rq_distances(x, codebook, norms):
+def rq_distances(x, codebook, norms, out=None):
     """x (n_vec, dim) fp32, codebook (K, dim) fp32 -> (n_vec, K) fp32 squared distances ||x||^2 + ||c||^2 - 2 x.c:
-    VQEmbedding.compute_distances (quantizations.py:43-62), the values the quantiser's argmin is taken over."""
+    VQEmbedding.compute_distances (quantizations.py:43-62), the values the quantiser's argmin is taken over.  out: buffer to write into."""
     n_vec, dim = x.shape
     K = codebook.shape[0]
-    out = torch.empty((n_vec, K), dtype=torch.float32, device=x.device)
+    out = _out_like(out, (n_vec, K), torch.float32, x.device, 'rq_distances')
     ws = torch.empty((max(n_vec, 1) * 512,), dtype=torch.uint8, device=x.device)
     with on_device_of(x):
         check(lib().rqamd_rq_distances(ptr(x, torch.float32), ptr(codebook, torch.float32), ptr(norms, torch.float32), K, n_vec, dim,

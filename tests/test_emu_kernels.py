@@ -103,17 +103,19 @@ def test_emu_rq_quantize_non_finite_rows(nat):
         assert np.array_equal(codes[keep], good.numpy()[keep])
 
 
-@pytest.mark.parametrize('which', ['ragged', 'split'])
+@pytest.mark.parametrize('which', ['golden', 'ragged', 'split', 'dims'])
 def test_emu_rq_quantize_codebook_dma_lands_late(nat, golden, monkeypatch, which):
     """Round 6: the quantiser's codebook ring (four 32-KB stages + the tile's norms, filled by LDS-DMA) with RQ_EMU_DMA=late -- every
     DMA lands only when the issuing lane's counted `s_waitcnt vmcnt(N)` retires it, so a fragment (or norm) read that is not behind the
     covering wait and the barrier returns stale bytes.  The default mode lands a DMA at issue (the worst case for a stage refilled while
-    some wavefront still reads it); the three tests above run in that mode.  Depths 1, 2 and 4 chunks per tile, ragged K, the split form."""
+    some wavefront still reads it); the tests above and below run in that mode.  1, 2, 3 and 4 chunks per tile, ragged K, the split form."""
     monkeypatch.setenv('RQ_EMU_DMA', 'late')
     if which == 'golden':
         test_emu_rq_quantize_and_embed(nat, golden)
     elif which == 'ragged':
         test_emu_rq_quantize_ragged(nat)
+    elif which == 'dims':
+        test_emu_rq_quantize_dims_and_tiny_codebooks(nat)
     else:
         test_emu_rq_quantize_codebook_split(nat)
 
