@@ -1432,6 +1432,7 @@ static __device__ __forceinline__ int blk_excl_scan(int v, int* redi, int* total
 static __device__ __forceinline__ unsigned order_key(float f) {   // monotone float -> uint, NaN on top (torch.topk)
     unsigned u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if (u == 0x80000000u) u = 0u;       // -0.0 == +0.0 (utils.py:60-64 compares floats): one key, or a threshold of +0.0 drops every -0.0
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -1583,6 +1584,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     // p >= 1 keeps every token: the reference's `cum_probs >= 1.0` can only fire through fp32 cumsum rounding
     // (mass of a few ulp), which no reordering of the sum reproduces -- the filter is skipped.
     if (p.top_p >= 0.f && p.top_p < 1.0f) {
+        // top_p = 0 keeps the first sorted token (its preceding mass, 0, is not below p; utils.py:72-75): searched as the smallest
+        // positive p, or `mass >= 0` would hold for every candidate, tau would end above every probability and the row at 0 / 0
+        const float top_p = fmaxf(p.top_p, 1.17549435e-38f);
         unsigned cur = 0;
         const bool in_regs = V <= SMP_T * SMP_VPT;
         float pv[SMP_VPT];
@@ -1610,7 +1614,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
                 for (int i = tid; i < V; i += SMP_T) { const float q = sx[i]; if (q >= cv) g += q; }
             }
             g = blk_sum_pp(g, red2, bit);
-            if (g >= p.top_p) cur = cand;
+            if (g >= top_p) cur = cand;
         }
         const float tau = __uint_as_float(cur);
         // boundary value, strict mass above it, number of ties at it
@@ -1626,7 +1630,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
         int rank = blk_excl_scan(nt, redi, &ntie);
         int need = ntie;
         if (vmin > 0.f) {
-            float m = ceilf((p.top_p - gs) / vmin);
+            float m = ceilf((top_p - gs) / vmin);
             if (m < 1.f) m = 1.f;
             if (m < (float)ntie) need = (int)m;
         }
@@ -1754,6 +1758,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
     for (int k = 0; k < NV; ++k) q[k] = q[k] / z;
 
     if (p.top_p >= 0.f && p.top_p < 1.0f) {     // utils.py:67-79, see sample_kernel
+        const float top_p = fmaxf(p.top_p, 1.17549435e-38f);       // top_p = 0: the first sorted token, see sample_kernel
         unsigned cur = 0;
         for (int bit = 30; bit >= 0; --bit) {
             const unsigned cand = cur | (1u << bit);
@@ -1768,7 +1773,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
                 g3 += q[k + 3] >= cv ? q[k + 3] : 0.f;
             }
             const float g = blk_sum_pp((g0 + g1) + (g2 + g3), sh.red2, bit);
-            if (g >= p.top_p) cur = cand;
+            if (g >= top_p) cur = cand;
         }
         const float tau = __uint_as_float(cur);
         float vmin = 2.0f;
@@ -1784,7 +1789,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
         (void)blk_excl_scan(nt, sh.redi, &ntie);
         int need = ntie;
         if (vmin > 0.f) {
-            float m = ceilf((p.top_p - gs) / vmin);
+            float m = ceilf((top_p - gs) / vmin);
             if (m < 1.f) m = 1.f;
             if (m < (float)ntie) need = (int)m;
         }
