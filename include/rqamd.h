@@ -362,6 +362,31 @@ int rqamd_dbg_conv_in_bf16(const float* x, const float* w, const float* bias, in
  * C <= 512.  A (form, shape) pair outside these limits returns RQAMD_ERR_UNSUPPORTED. */
 int rqamd_dbg_vae_attn(const void* qkv, int B, int T, int C, int form, void* out, void* stream);
 
+/* The RQ-Transformer's attention launchers alone (csrc/rqt_kernels.hip), for the stand-alone fp64 checks of tests/rqt_attn_cases.py: each
+ * entry fills the launcher's argument struct and calls it unchanged, so the kernel is the one the engine would pick for these sizes
+ * (rqamd_dbg_set_row_scale and the RQAMD_ATTN_LONG / RQAMD_ATTN_LONG_SPLIT / RQAMD_PREFILL_TILED switches apply).  All 16-bit operands are
+ * bf16, head size = E / nh (64: the register / chunked kernels; anything else up to 256: the plain kernels).
+ *
+ * One decode step at position t: qkv [rows][3E] (q | k | v of this token), caches kc, vc [rows][nh][Tcap][hd] bf16, y [rows][E].  The
+ * token's k / v is appended at cache row t and attends over rows 0 .. t.  ksc != NULL: kc holds bytes with one fp32 scale per cached key
+ * in ksc [rows][nh][Tcap], component = (byte - 128) * scale; vsc != NULL (needs ksc): vc likewise.  t_max: the host bound on t that
+ * selects the kernel (-1 = Tcap - 1).  step_dev == NULL: t is passed by value; otherwise *step_dev is set to step_base on the stream
+ * first and the kernel reads t = *step_dev + (t - step_base), as a captured graph does.  Refused with RQAMD_ERR_INVALID before any launch
+ * (the kernels trap on a position outside the host bound): a null qkv or y, rows, nh, E or Tcap < 1, t < 0, t >= Tcap, t_max >= Tcap,
+ * 0 <= t_max < t, a missing kc or vc, vsc without ksc.  The launcher's own refusals pass through (RQAMD_ERR_UNSUPPORTED: 8-bit caches
+ * with Tcap > 256 or a head size other than 64, head size > 256, a head size other than 64 with Tcap > 256). */
+int rqamd_dbg_rqt_attn_decode(const void* qkv, void* kc, void* vc, float* ksc, float* vsc, int rows, int nh, int E, int Tcap, int t,
+                              int t_max, int* step_dev, int step_base, void* y, void* stream);
+/* The causal attention over a prefix of P tokens per image: qkv [n_img * P][3E], y [n_img * P][E]; the k / v of token i are appended at
+ * cache row i of caches laid out as above with rows = n_img (rows P .. Tcap-1 are not touched).  kc == NULL (with vc, ksc, vsc): the
+ * cache-free form.  Refused with RQAMD_ERR_INVALID: a null qkv or y, n_img, nh or E < 1, vsc without ksc, kc without vc, the cache-free
+ * form with another cache pointer; with RQAMD_ERR_UNSUPPORTED: P < 1, P > Tcap, 8-bit caches with P > 255, and the head-size limits above. */
+int rqamd_dbg_rqt_attn_prefill(const void* qkv, void* kc, void* vc, float* ksc, float* vsc, int n_img, int P, int nh, int E, int Tcap,
+                               void* y, void* stream);
+/* Causal attention inside groups of `group` consecutive rows (the depth axis of the head stack): qkv [rows][3E] -> y [rows][E].
+ * Refused with RQAMD_ERR_INVALID: a null qkv or y, E not a multiple of nh, group outside 1 .. 8, rows not a multiple of group. */
+int rqamd_dbg_rqt_attn_packed(const void* qkv, int rows, int group, int nh, int E, void* y, void* stream);
+
 /* Kernel variants are selected by the number of rows (batch).  factor > 1 makes the selection logic see rows * factor, so
  * that the large-batch variants run on test-sized inputs (results must not change); 1 restores normal behaviour. */
 int rqamd_dbg_set_row_scale(int factor);

@@ -288,6 +288,15 @@ static __device__ __forceinline__ float dot_q_bytes(const float* qf, rq_u64w w) 
     d = fmaf(qf[6], rq_ubyte_f32<2>(w.y), d); d = fmaf(qf[7], rq_ubyte_f32<3>(w.y), d);
     return d;
 }
+// acc[e] += w * (byte[e] - 128) over this lane's 8 value components.  The zero point leaves each byte before the product (exact: both are
+// small integers): taken out of the finished sum instead, as -128 * sum w, it cancels against w * byte at the magnitude of the largest
+// weight, and a component whose heavy rows sit at byte 128 lost every light row of the same key group (tests/rqt_attn_cases.py).
+static __device__ __forceinline__ void acc_bytes(float* acc, float w, rq_u64w vb) {
+    acc[0] = fmaf(w, rq_ubyte_f32<0>(vb.x) - 128.0f, acc[0]); acc[1] = fmaf(w, rq_ubyte_f32<1>(vb.x) - 128.0f, acc[1]);
+    acc[2] = fmaf(w, rq_ubyte_f32<2>(vb.x) - 128.0f, acc[2]); acc[3] = fmaf(w, rq_ubyte_f32<3>(vb.x) - 128.0f, acc[3]);
+    acc[4] = fmaf(w, rq_ubyte_f32<0>(vb.y) - 128.0f, acc[4]); acc[5] = fmaf(w, rq_ubyte_f32<1>(vb.y) - 128.0f, acc[5]);
+    acc[6] = fmaf(w, rq_ubyte_f32<2>(vb.y) - 128.0f, acc[6]); acc[7] = fmaf(w, rq_ubyte_f32<3>(vb.y) - 128.0f, acc[7]);
+}
 static __device__ __forceinline__ float group8_sum(float v) {
     v += rq_dpp_xor1(v);
     v += rq_dpp_xor2(v);
@@ -307,7 +316,7 @@ static __device__ __forceinline__ float group8_sum(float v) {
 // all P pairs are in flight together: at short contexts a wavefront's lifetime is one memory round trip, and with
 // 98 304 pairs per launch the launch time was 12 rounds of 8192 resident wavefronts x that latency (45 us at t = 0).
 // VQ (round 6, opt-in RQAMD_KV=int8kv; implies KQ): the cached VALUES are bytes + one scale per (token, head) as well -- out = sum_j p_j
-// scale_j (byte_j - 128) is accumulated as sum_j w_j byte_j - 128 sum_j w_j with w_j = p_j scale_j; this token's own value is used as
+// scale_j (byte_j - 128) is accumulated as sum_j w_j (byte_j - 128) with w_j = p_j scale_j (acc_bytes); this token's own value is used as
 // it comes out of the qkv GEMM (bf16) and quantised only on its way into the cache.
 template <int NJ, bool DYN, int P, bool KQ = false, bool VQ = false>
 static __device__ __forceinline__ void attn_run(const AttnDecodeArgs& p, int lane, int b, int h0, int t) {
@@ -465,7 +474,6 @@ static __device__ __forceinline__ void attn_run(const AttnDecodeArgs& p, int lan
         float acc[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        float wsum = 0.f;
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) {
             if (DYN && jj >= nblk) continue;
@@ -473,12 +481,7 @@ static __device__ __forceinline__ void attn_run(const AttnDecodeArgs& p, int lan
             if constexpr (VQ) {
                 const int j = jj * 8 + g;
                 const float w = j < t ? pj * vsv[i][jj] : 0.f;      // cached rows: weight x scale on the bytes
-                const rq_u64w vb = vr8[i][jj];
-                acc[0] = fmaf(w, rq_ubyte_f32<0>(vb.x), acc[0]); acc[1] = fmaf(w, rq_ubyte_f32<1>(vb.x), acc[1]);
-                acc[2] = fmaf(w, rq_ubyte_f32<2>(vb.x), acc[2]); acc[3] = fmaf(w, rq_ubyte_f32<3>(vb.x), acc[3]);
-                acc[4] = fmaf(w, rq_ubyte_f32<0>(vb.y), acc[4]); acc[5] = fmaf(w, rq_ubyte_f32<1>(vb.y), acc[5]);
-                acc[6] = fmaf(w, rq_ubyte_f32<2>(vb.y), acc[6]); acc[7] = fmaf(w, rq_ubyte_f32<3>(vb.y), acc[7]);
-                wsum += w;
+                acc_bytes(acc, w, vr8[i][jj]);
                 const float ps = j < t ? 0.f : pj;                  // this token's own row (j == t; 0 beyond it), bf16
                 float vf[8];
                 unpack8(vn_all[i], vf);
@@ -490,10 +493,6 @@ static __device__ __forceinline__ void attn_run(const AttnDecodeArgs& p, int lan
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, vf[e], acc[e]);
             }
-        }
-        if constexpr (VQ) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = fmaf(-128.0f, wsum, acc[e]);      // the bytes' zero point
         }
         // Reduce-scatter over the 8 key groups so that every lane ends with ONE of the 64 outputs (6 cross-row
         // shuffles instead of 24: the ds_bpermute count, 2.4 M per launch, was the LDS pipe's whole budget):
@@ -617,28 +616,17 @@ static __device__ __forceinline__ void attn_small_run(const AttnDecodeArgs& p, l
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    float wsum = 0.f;
 #pragma unroll
     for (int j = 0; j <= T; ++j) {
         const float pj = sc[j] * inv;
         if (VQ && j < T) {
-            const float w = pj * vsv[j < T ? j : 0];
-            const rq_u64w vb = vr8[j < T ? j : 0];
-            acc[0] = fmaf(w, rq_ubyte_f32<0>(vb.x), acc[0]); acc[1] = fmaf(w, rq_ubyte_f32<1>(vb.x), acc[1]);
-            acc[2] = fmaf(w, rq_ubyte_f32<2>(vb.x), acc[2]); acc[3] = fmaf(w, rq_ubyte_f32<3>(vb.x), acc[3]);
-            acc[4] = fmaf(w, rq_ubyte_f32<0>(vb.y), acc[4]); acc[5] = fmaf(w, rq_ubyte_f32<1>(vb.y), acc[5]);
-            acc[6] = fmaf(w, rq_ubyte_f32<2>(vb.y), acc[6]); acc[7] = fmaf(w, rq_ubyte_f32<3>(vb.y), acc[7]);
-            wsum += w;
+            acc_bytes(acc, pj * vsv[j < T ? j : 0], vr8[j < T ? j : 0]);
         } else {
             float vf[8];
             unpack8((!VQ && j < T) ? vr[(!VQ && j < T) ? j : 0] : vn, vf);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, vf[e], acc[e]);
         }
-    }
-    if constexpr (VQ) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(-128.0f, wsum, acc[e]);
     }
     if (valid) {
         rq_u128 o;
@@ -2459,5 +2447,50 @@ int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
     if (a.V < 1 || a.t_per < 1) return rq_fail(RQAMD_ERR_INVALID, "log_prob: V = %d, t_per = %d", a.V, a.t_per);
     RQ_LAUNCH(log_prob_kernel, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
     return rq_check_launch("log_prob_kernel");
+}
+
+// -------------------------------------------------------------------------------------------------
+// diagnostics (include/rqamd.h): the attention launchers alone, for the stand-alone fp64 checks (tests/rqt_attn_cases.py).  Each entry
+// fills the launcher's argument struct and calls it unchanged; what the kernels would trap on is refused here, before any launch.
+extern "C" int rqamd_dbg_rqt_attn_decode(const void* qkv, void* kc, void* vc, float* ksc, float* vsc, int rows, int nh, int E, int Tcap,
+                                         int t, int t_max, int* step_dev, int step_base, void* y, void* stream) {
+    if (!qkv || !y) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: null qkv or y");
+    if (rows < 1 || nh < 1 || E < 1 || Tcap < 1)
+        return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: rows %d, n_head %d, embed_dim %d, Tcap %d (each >= 1)", rows, nh, E, Tcap);
+    if (t < 0 || t >= Tcap) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: t %d outside the cache (0 .. %d)", t, Tcap - 1);
+    if (t_max >= Tcap) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: t_max %d outside the cache (Tcap %d)", t_max, Tcap);
+    if (t_max >= 0 && t > t_max) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: t %d > t_max %d", t, t_max);
+    if (!kc || !vc) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: a decode step needs a key cache and a value cache");
+    if (vsc && !ksc) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_decode: value scales without key scales (8-bit values come with 8-bit keys)");
+    hipStream_t s = (hipStream_t)stream;
+    AttnDecodeArgs a;
+    a.qkv = (const bf16_t*)qkv; a.kc = (bf16_t*)kc; a.vc = (bf16_t*)vc; a.ksc = ksc; a.vsc = vsc; a.y = (bf16_t*)y;
+    a.step = nullptr; a.step_off = t; a.t_max = t_max;
+    a.rows = rows; a.nh = nh; a.E = E; a.Tcap = Tcap;
+    if (step_dev) {                                   // t = *step_dev + step_off, as the engine's captured graphs pass it
+        RQ_TRY(rq_launch_set_int(step_dev, step_base, s));
+        a.step = step_dev;
+        a.step_off = t - step_base;
+    }
+    return rq_launch_attn_decode(a, s);
+}
+
+extern "C" int rqamd_dbg_rqt_attn_prefill(const void* qkv, void* kc, void* vc, float* ksc, float* vsc, int n_img, int P, int nh, int E,
+                                          int Tcap, void* y, void* stream) {
+    if (!qkv || !y) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_prefill: null qkv or y");
+    if (n_img < 1 || nh < 1 || E < 1) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_prefill: %d images, n_head %d, embed_dim %d (each >= 1)", n_img, nh, E);
+    if (vsc && !ksc) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_prefill: value scales without key scales (8-bit values come with 8-bit keys)");
+    AttnPrefillArgs a;
+    a.qkv = (const bf16_t*)qkv; a.kc = (bf16_t*)kc; a.vc = (bf16_t*)vc; a.ksc = ksc; a.vsc = vsc; a.y = (bf16_t*)y;
+    a.n_img = n_img; a.P = P; a.nh = nh; a.E = E; a.Tcap = Tcap;
+    return rq_launch_attn_prefill(a, (hipStream_t)stream);
+}
+
+extern "C" int rqamd_dbg_rqt_attn_packed(const void* qkv, int rows, int group, int nh, int E, void* y, void* stream) {
+    if (!qkv || !y) return rq_fail(RQAMD_ERR_INVALID, "dbg_rqt_attn_packed: null qkv or y");
+    AttnPackedArgs a;
+    a.qkv = (const bf16_t*)qkv; a.y = (bf16_t*)y;
+    a.rows = rows; a.group = group; a.nh = nh; a.E = E;
+    return rq_launch_attn_packed(a, (hipStream_t)stream);
 }
 #endif  // !RQ_SAMPLE_ONLY_TU

@@ -116,6 +116,11 @@ _SIGS = {
     'rqamd_dbg_conv_out_bf16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p]),
     'rqamd_dbg_vae_attn': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_rqt_attn_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_rqt_attn_prefill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_rqt_attn_packed': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -517,6 +522,38 @@ def dbg_vae_attn(qkv, form=0, out=None):
     with on_device_of(qkv):
         check(lib().rqamd_dbg_vae_attn(ptr(qkv, torch.bfloat16), B, T, C3 // 3, int(form), ptr(out, torch.bfloat16), stream_of(qkv)))
     return out
+
+
+def dbg_rqt_attn_decode(qkv, kc, vc, y, nh, Tcap, t, t_max=-1, ksc=None, vsc=None, step=None, step_base=0):
+    """diagnostics: one decode step of the RQ-Transformer's attention alone (include/rqamd.h: rqamd_dbg_rqt_attn_decode).  qkv (rows, 3E)
+    bf16, y (rows, E) bf16, caches (rows, nh, Tcap, hd) bf16 -- or uint8 with fp32 scales ksc / vsc (rows, nh, Tcap); step: a one-element
+    int32 tensor through which t reaches the kernel (set to step_base first), or None."""
+    rows, E3 = qkv.shape
+    with on_device_of(qkv):
+        check(lib().rqamd_dbg_rqt_attn_decode(ptr(qkv, torch.bfloat16), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
+                                              rows, int(nh), E3 // 3, int(Tcap), int(t), int(t_max), ptr(step, torch.int32), int(step_base),
+                                              ptr(y, torch.bfloat16), stream_of(qkv)))
+    return y
+
+
+def dbg_rqt_attn_prefill(qkv, y, n_img, P, nh, Tcap, kc=None, vc=None, ksc=None, vsc=None):
+    """diagnostics: the causal prefix attention alone (rqamd_dbg_rqt_attn_prefill).  qkv (n_img * P, 3E) bf16, y (n_img * P, E) bf16,
+    caches as dbg_rqt_attn_decode with rows = n_img, or none at all (the cache-free form)."""
+    with on_device_of(qkv):
+        check(lib().rqamd_dbg_rqt_attn_prefill(ptr(qkv, torch.bfloat16), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
+                                               int(n_img), int(P), int(nh), qkv.shape[-1] // 3, int(Tcap), ptr(y, torch.bfloat16),
+                                               stream_of(qkv)))
+    return y
+
+
+def dbg_rqt_attn_packed(qkv, y, group, nh):
+    """diagnostics: causal attention inside groups of `group` <= 8 consecutive rows (rqamd_dbg_rqt_attn_packed).  qkv (rows, 3E) bf16,
+    y (rows, E) bf16."""
+    rows, E3 = qkv.shape
+    with on_device_of(qkv):
+        check(lib().rqamd_dbg_rqt_attn_packed(ptr(qkv, torch.bfloat16), rows, int(group), int(nh), E3 // 3, ptr(y, torch.bfloat16),
+                                              stream_of(qkv)))
+    return y
 
 
 # ---------------------------------------------------------------------------------------------- engines

@@ -64,6 +64,51 @@ def test_status_codes_without_gpu(lib_path):
     assert lib.rqamd_rq_quantize(None, None, None, None, 4, 0, 256, None, None, None, 0, None) == 0     # empty input is a no-op
 
 
+def test_rqt_attn_diagnostics_refuse_without_gpu(lib_path):
+    """rqamd_dbg_rqt_attn_decode / _prefill / _packed refuse, before any HIP call, whatever would make a kernel trap or write outside its
+    buffers -- and the launchers' own refusals pass through with their messages.  Every call here is refused: the pointers are never read."""
+    from rqvae import _native
+    lib = _native._bind(lib_path)
+    err = lambda: lib.rqamd_last_error().decode()
+    p = ctypes.c_void_p(4096)                                   # any non-null value
+
+    def dec(qkv=p, kc=p, vc=p, ksc=None, vsc=None, rows=2, nh=3, E=192, Tcap=64, t=5, t_max=63, step=None, y=p):
+        return lib.rqamd_dbg_rqt_attn_decode(qkv, kc, vc, ksc, vsc, rows, nh, E, Tcap, t, t_max, step, 0, y, None)
+    for kw, word in ((dict(qkv=None), 'null'), (dict(y=None), 'null'), (dict(rows=0), 'rows 0'), (dict(nh=0), 'n_head 0'), (dict(Tcap=0), 'Tcap 0'),
+                     (dict(E=0), 'embed_dim 0'), (dict(t=-1), 't -1 outside'), (dict(t=64), 't 64 outside'), (dict(t=63, t_max=64), 't_max 64'),
+                     (dict(t=9, t_max=8), 't 9 > t_max 8'), (dict(t=8, t_max=7), 't 8 > t_max 7'), (dict(vc=None), 'value cache'),
+                     (dict(kc=None), 'key cache'), (dict(vsc=p), 'without key scales'), (dict(t=0, t_max=0, step=p, Tcap=0), 'Tcap 0')):
+        assert dec(**kw) == -1, kw
+        assert word in err(), (kw, err())
+    # the launcher's refusals, unchanged
+    for kw, word in ((dict(ksc=p, Tcap=320, t_max=319), 'end at 256 keys'), (dict(ksc=p, vsc=p, Tcap=320, t_max=100), 'end at 256 keys'),
+                     (dict(nh=1, E=257), 'head_dim 257 > 256'), (dict(nh=3, E=240, Tcap=257, t_max=256), 'context 257 > 256'),
+                     (dict(nh=3, E=240, ksc=p), 'written for head_dim 64'), (dict(nh=3, E=100), 'not a multiple of n_head')):
+        assert dec(**kw) in (-1, -2), kw
+        assert word in err(), (kw, err())
+    assert dec(nh=3, E=100) == -1 and dec(nh=1, E=257) == -2
+
+    def pre(qkv=p, kc=p, vc=p, ksc=None, vsc=None, n_img=2, P=4, nh=3, E=192, Tcap=8, y=p):
+        return lib.rqamd_dbg_rqt_attn_prefill(qkv, kc, vc, ksc, vsc, n_img, P, nh, E, Tcap, y, None)
+    for kw, code, word in ((dict(qkv=None), -1, 'null'), (dict(y=None), -1, 'null'), (dict(n_img=0), -1, '0 images'), (dict(nh=0), -1, 'n_head 0'),
+                           (dict(vsc=p), -1, 'without key scales'), (dict(vc=None), -1, 'without a value cache'),
+                           (dict(kc=None), -1, 'cache-free form with a cache pointer'), (dict(kc=None, vc=None, ksc=p), -1, 'cache-free form'),
+                           (dict(P=9), -2, '9 tokens (cache 8)'), (dict(P=0), -2, '0 tokens'), (dict(P=256, Tcap=256, ksc=p), -2, '255 prefix tokens'),
+                           (dict(P=256, Tcap=256, ksc=p, vsc=p), -2, '255 prefix tokens'), (dict(E=240, P=9), -2, '9 tokens (cache 8)'),
+                           (dict(E=240, Tcap=257), -2, 'context 257 > 256'), (dict(E=240, ksc=p), -2, 'written for head_dim 64'),
+                           (dict(nh=1, E=257), -2, 'head_dim 257 > 256')):
+        assert pre(**kw) == code, kw
+        assert word in err(), (kw, err())
+
+    def pack(qkv=p, rows=16, group=4, nh=2, E=128, y=p):
+        return lib.rqamd_dbg_rqt_attn_packed(qkv, rows, group, nh, E, y, None)
+    for kw, code, word in ((dict(qkv=None), -1, 'null'), (dict(y=None), -1, 'null'), (dict(group=9, rows=18), -1, '18 rows in groups of 9'),
+                           (dict(group=0), -1, 'groups of 0'), (dict(rows=17), -1, '17 rows in groups of 4'), (dict(rows=0), -1, '0 rows'),
+                           (dict(nh=0), -1, 'n_head 0'), (dict(nh=3, E=128), -1, 'not a multiple'), (dict(nh=1, E=257), -2, 'head_dim 257 > 256')):
+        assert pack(**kw) == code, kw
+        assert word in err(), (kw, err())
+
+
 def test_no_cpu_fallback(lib_path, monkeypatch):
     from rqvae import _native
     with pytest.raises(_native.RqamdError, match='CPU'):
