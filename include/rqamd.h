@@ -126,6 +126,19 @@ int rqamd_sample_logits(const float* logits, int rows, int vocab, float temperat
 int rqamd_sample_logits_rows(const float* logits, int rows, int vocab, const float* temperature, const int* top_k,
                              const float* top_p, const uint64_t* seeds, uint64_t seed, uint64_t offset,
                              int64_t* samples_out, float* probs_out, int* row_flags, void* stream);
+/* The draw and its log-probability (not in the reference); additive, ABI v7.  One entry point for the four forms of the sampler:
+ * logits_u NULL: unguided, else row r is drawn from guide(logits[r], logits_u[r], s) as rqamd_rqt_sample_guided draws it, s =
+ * guidance_scale or row_gscale[r]; row_temperature NULL: the scalar kernels with temperature / top_k / top_p, else the per-row kernels
+ * with the DEVICE arrays row_temperature, row_top_k, row_top_p (both required then), row_gscale and row_seeds (each or NULL), as in
+ * rqamd_sample_logits_rows.  samples_out (rows) int64 and draw_logp_out (rows) fp32 are both required: samples_out is bit for bit
+ * what the entry point without log-probabilities draws from the same arguments, and draw_logp_out[r] = log of the probability the
+ * drawn code had in the distribution row r was drawn from (after guidance, temperature, top-k, top-p and renormalisation; +0.0
+ * where one code survives).  row_flags as above. */
+int rqamd_sample_logits_logp(const float* logits, const float* logits_u, int rows, int vocab,
+                             float temperature, int top_k, float top_p, float guidance_scale,
+                             const float* row_temperature, const int* row_top_k, const float* row_top_p,
+                             const float* row_gscale, const uint64_t* row_seeds, uint64_t seed, uint64_t offset,
+                             int64_t* samples_out, float* draw_logp_out, int* row_flags, void* stream);
 
 /* ---- RQ-VAE encoder / decoder engine -------------------------------------------------------
  * Handle = packed bf16 weights + activation workspace for Encoder/Decoder (modules.py:10-202),
@@ -258,6 +271,20 @@ int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const uint8_t* k
                           int start_h, int start_w, const float* temperature, const int* top_k, const float* top_p,
                           const float* guidance_scale, const uint64_t* seeds, uint64_t seed, uint64_t offset,
                           int use_graph, int64_t* codes_out, void* stream);
+/* Log-probabilities of the draws (not in the reference); additive, ABI v7.  Arms the NEXT rqamd_rqt_sample, _masked, _guided or
+ * _rows call on the handle; that call consumes the arming whether it succeeds or fails.  Each output is a device pointer to
+ * (batch, H, W, D) fp32 or NULL; all NULL disarms.  The armed call returns, bit for bit, the codes of the unarmed call with the same
+ * arguments, seed and offset, and after it
+ *   draw[b,h,w,d]   = log of the probability, in the distribution the draw was made from (logits after guidance, temperature, top-k,
+ *                     top-p and renormalisation), of the code that was drawn; +0.0 for every code that was not drawn (kept codes,
+ *                     codes before start_h / start_w);
+ *   model[b,h,w,d]  = log_softmax of row b's raw logits (before guidance and temperature, per-depth vocabulary mask applied) at the
+ *                     code, drawn or kept; NaN where the head stack did not run (positions before the start, positions that
+ *                     pos_active_host promises away);
+ *   model_uncond    = the same for the unconditional twin rows batch + b; with an unguided call it is RQAMD_ERR_INVALID.
+ * The values are written into the handle's workspace and copied out next to codes_out, so captured graphs never hold a caller's
+ * pointer.  Armed calls replay graph sets of their own: alternating armed and unarmed calls recaptures nothing. */
+int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* model_logp_out, float* model_logp_uncond_out);
 /* *captures = the number of position graphs this handle has captured so far (every form of sampling); a call that replays only
  * leaves it unchanged. */
 int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures);

@@ -90,6 +90,10 @@ struct rqamd_rqt {
     float* row_tp;              // [rows][D]
     uint64_t* row_seed;         // [rows]
     std::vector<char> row_host; // host staging of the five arrays: outlives the asynchronous copies of the call that filled it
+    // log-probabilities of an armed call (rqamd_rqt_sample_logp), laid out like xs: filled before the position loop (draw 0, model NaN), written
+    // by the LOGP samplers and the step form of log_prob_kernel, copied out next to the codes -- the captured graphs hold these addresses
+    float *logp_draw, *logp_model;      // [rows][HW][D]
+    struct LogpArm { float *draw, *model, *model_u; bool on() const { return draw || model || model_u; } } arm = {};   // outputs of the next sampling call
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -108,9 +112,10 @@ struct rqamd_rqt {
     // kernel argument of the captured launch, so seeded calls must never replay unseeded graphs, and neither recaptures the other's.  Their
     // sampler launches read every parameter from h->row_*, so their keys hold no parameter value (T, gs, tk, tp stay zero): rows,
     // codebooks, stream and the guided flag only, and a call with other values replays what is there.  Scalar and per-row families
-    // never invalidate each other.
+    // never invalidate each other.  Armed calls (rqamd_rqt_sample_logp: other sampler kernels and one more launch per step) are six
+    // more families, gkey[6] .. gkey[11] and sets [12] .. [23], in the same order: alternating armed and unarmed calls recaptures nothing.
     static constexpr int NGRAPH = 33;
-    static constexpr int NFAM = 6;
+    static constexpr int NFAM = 12;
     hipGraphExec_t gexec[2 * NFAM][NGRAPH] = {};
     struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey[NFAM];
     bool gkey_set[NFAM] = {}, gstale[NFAM] = {};
@@ -142,6 +147,10 @@ __global__ void bias_table_kernel(const float* bias, float scale, const float* p
 }
 __global__ void set_rng_kernel(uint64_t* rng, uint64_t seed, uint64_t offset) {
     if (threadIdx.x == 0) { rng[0] = seed; rng[1] = offset; }
+}
+__global__ void fill_f32_kernel(float* p, float v, long n) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid < n) p[gid] = v;
 }
 
 static size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -412,7 +421,7 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + al(brows * V * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
                    + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4)
                    + al(brows * h->HW * h->D)
-                   + 2 * al(brows * 4) + 2 * al(brows * h->D * 4) + al(brows * 8);
+                   + 2 * al(brows * 4) + 2 * al(brows * h->D * 4) + al(brows * 8) + 2 * al(brows * h->HW * h->D * 4);
     RQ_TRY(h->ws.reserve(total));
     char* p = (char*)h->ws.p;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
@@ -428,6 +437,7 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     h->row_T = (float*)take(brows * 4); h->row_gs = (float*)take(brows * 4);
     h->row_tk = (int*)take(brows * h->D * 4); h->row_tp = (float*)take(brows * h->D * 4);
     h->row_seed = (uint64_t*)take(brows * 8);
+    h->logp_draw = (float*)take(brows * h->HW * h->D * 4); h->logp_model = (float*)take(brows * h->HW * h->D * 4);
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
     const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
     // (8-bit keys: half the bytes for K plus one fp32 scale per (row, head, position))
@@ -582,6 +592,7 @@ struct StepCtx {
     float gscale;
     bool per_row;          // rqamd_rqt_sample_rows: the sampler reads temperature / top_k / top_p (and gscale when guided) of each row from
     bool row_seeds;        //   h->row_*, and with row_seeds the Philox key from h->row_seed; the scalars above are unused
+    bool logp;             // armed call (rqamd_rqt_sample_logp): the LOGP samplers write h->logp_draw, a step log_prob launch h->logp_model
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -680,7 +691,16 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
             s.row_gscale = c.guided ? h->row_gs : nullptr;
             if (c.row_seeds) { s.row_seeds = h->row_seed; s.rng = nullptr; }      // key row_seed[b], counter 0 + slot (s.offset is 0)
         }
+        if (c.logp) s.logp_out = h->logp_draw;
         RQ_TRY(rq_launch_sample(s, st));
+        if (c.logp) {
+            // log_softmax(raw logits of the row)[code] for every row of the step (both twins of a guided pair), drawn and kept codes alike:
+            // the logits the sampler saw, before guidance and temperature, LogitMask columns at -inf
+            LogProbArgs lp{};
+            lp.logits = h->logits; lp.ld = h->V; lp.rows = B; lp.V = h->V; lp.targets = h->xs; lp.t_per = 1; lp.t_stride = h->HW * h->D;
+            lp.out = h->logp_model; lp.pos = h->st; lp.slot_D = h->D; lp.slot_d = d;
+            RQ_TRY(rq_launch_log_prob(lp, st));
+        }
     } else if (c.logits_out) {
         float* dst = c.logits_out + ((long)host_pos * h->D + d) * h->V;
         RQ_HIP(hipMemcpy2DAsync(dst, (size_t)h->HW * h->D * h->V * 4, h->logits, (size_t)h->V * 4, (size_t)h->V * 4, B,
@@ -749,7 +769,7 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
 // positions before start_idx.  Nothing runs after the last active position -- nobody reads its KV entries.
 static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, const int64_t* cond, int start_idx, bool use_graph,
                    int64_t* codes_out, hipStream_t st, const uint8_t* keep = nullptr, const uint8_t* pos_active = nullptr,
-                   const int64_t* uncond = nullptr) {
+                   const int64_t* uncond = nullptr, rqamd_rqt::LogpArm arm = {}) {
     StepCtx c = c_in;
     const int n_in = c.guided ? c.Bs : c.B;              // rows of the caller's arrays (guided: the engine runs c.B = 2 * n_in rows)
     RQ_TRY(begin_batch(h, c, partial, cond, st, uncond));
@@ -761,7 +781,13 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         c.keep = h->keep;
         while (pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
     }
-    const int fam = (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
+    if (c.logp) {          // outside any capture: what no step writes stays +0.0 (draw: kept codes, codes before start_idx) / NaN (model: no head ran)
+        const long n = (long)c.B * h->HW * h->D;
+        RQ_HIP(hipMemsetAsync(h->logp_draw, 0, (size_t)n * 4, st));
+        RQ_LAUNCH(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->logp_model, __builtin_nanf(""), n);
+        RQ_TRY(rq_check_launch("fill_f32_kernel"));
+    }
+    const int fam = (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = 0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
@@ -809,11 +835,28 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         RQ_TRY(rq_launch_add_int(h->st, 1, st));
     }
     if (codes_out) RQ_HIP(hipMemcpyAsync(codes_out, h->xs, (size_t)n_in * h->HW * h->D * 8, hipMemcpyDeviceToDevice, st));
+    if (c.logp) {
+        const size_t lb = (size_t)n_in * h->HW * h->D * 4;
+        if (arm.draw) RQ_HIP(hipMemcpyAsync(arm.draw, h->logp_draw, lb, hipMemcpyDeviceToDevice, st));
+        if (arm.model) RQ_HIP(hipMemcpyAsync(arm.model, h->logp_model, lb, hipMemcpyDeviceToDevice, st));
+        if (arm.model_u) RQ_HIP(hipMemcpyAsync(arm.model_u, h->logp_model + (size_t)n_in * h->HW * h->D, lb, hipMemcpyDeviceToDevice, st));
+    }
     return RQAMD_OK;
 }
 
 // host arrays of rqamd_rqt_sample_rows (batch rows each; top_k / top_p batch * D)
 struct RowParams { const float* temperature; const int* top_k; const float* top_p; const float* gscale; const uint64_t* seeds; };
+
+// the arming of rqamd_rqt_sample_logp, taken by the next sampling call whether it succeeds or fails
+static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
+    const rqamd_rqt::LogpArm a = h->arm;
+    h->arm = {};
+    return a;
+}
+struct ArmGuard {          // an entry point that returns before sample_impl still consumes the arming
+    rqamd_rqt* h;
+    ~ArmGuard() { if (h) h->arm = {}; }
+};
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
 // 2 * batch engine rows (rows batch.. conditioned on `uncond`), drawn from the guided logits with scale `gscale`
@@ -823,11 +866,13 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
                        bool guided = false, const int64_t* uncond = nullptr, float gscale = 1.f, const RowParams* rp = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     h->step_on = false;
+    const rqamd_rqt::LogpArm arm = take_arm(h);        // (consumed here at the latest: the entry points take it before their own checks)
+    if (arm.model_u && !guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: model_logp_uncond_out armed for an unguided call");
     const int rows = guided ? 2 * batch : batch;
     RQ_TRY(ensure_batch(h, rows));
     StepCtx c{};
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
-    c.guided = guided; c.Bs = batch; c.gscale = gscale;
+    c.guided = guided; c.Bs = batch; c.gscale = gscale; c.logp = arm.on();
     if (rp) {
         // per-row values: host arrays -> one staging block owned by the handle -> h->row_* by asynchronous copies ahead of the position
         // loop on the same stream, outside any capture.  The caller's arrays are read before this function returns; the staging block
@@ -859,11 +904,11 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
         k.T = temperature; k.gs = guided ? gscale : 0.f;
         for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
     }
-    const int fam = (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
+    const int fam = (arm.on() ? 6 : 0) + (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
     if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
-    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st, keep, pos_active, uncond));
+    RQ_TRY(run_all(h, c, partial, cond, start_idx, use_graph != 0, codes_out, st, keep, pos_active, uncond, arm));
     if (h->prof.on) {
         RQ_HIP(hipStreamSynchronize(st));
         double ms = 0;
@@ -890,6 +935,7 @@ extern "C" int rqamd_rqt_sample(rqamd_rqt* h, const int64_t* partial, const int6
                                 const float* const* codebooks, int start_h, int start_w, float temperature,
                                 const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
                                 int use_graph, int64_t* codes_out, void* stream) {
+    ArmGuard arm_guard{h};
     if (!h || !partial || !codebooks || !top_k || !top_p || !codes_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: null argument");
     if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: batch < 1");
     if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample: temperature must be > 0");
@@ -907,6 +953,7 @@ extern "C" int rqamd_rqt_sample_masked(rqamd_rqt* h, const int64_t* partial, con
                                        const int64_t* cond, int batch, const float* const* codebooks, float temperature,
                                        const int* top_k, const float* top_p, uint64_t seed, uint64_t offset,
                                        int use_graph, int64_t* codes_out, void* stream) {
+    ArmGuard arm_guard{h};
     if (!h || !partial || !keep || !codebooks || !top_k || !top_p || !codes_out)
         return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: null argument");
     if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_masked: batch < 1");
@@ -922,6 +969,7 @@ extern "C" int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, con
                                        const int64_t* cond, const int64_t* uncond, int batch, const float* const* codebooks,
                                        int start_h, int start_w, float temperature, float guidance_scale, const int* top_k,
                                        const float* top_p, uint64_t seed, uint64_t offset, int use_graph, int64_t* codes_out, void* stream) {
+    ArmGuard arm_guard{h};
     if (!h || !partial || !codebooks || !top_k || !top_p || !codes_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: null argument");
     if (batch < 1 || batch > 0x3fffffff) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: batch < 1 (or 2 * batch overflows)");
     if (!(temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_guided: temperature must be > 0");
@@ -940,6 +988,7 @@ extern "C" int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const
                                      int start_h, int start_w, const float* temperature, const int* top_k, const float* top_p,
                                      const float* guidance_scale, const uint64_t* seeds, uint64_t seed, uint64_t offset,
                                      int use_graph, int64_t* codes_out, void* stream) {
+    ArmGuard arm_guard{h};
     if (!h || !partial || !codebooks || !temperature || !top_k || !top_p || !codes_out)
         return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: null argument");
     if (batch < 1 || batch > 0x3fffffff) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_rows: batch < 1 (or 2 * batch overflows)");
@@ -958,6 +1007,15 @@ extern "C" int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const
     static const float no_p[8] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
     return sample_impl(h, partial, keep, keep ? pos_active_host : nullptr, cond, batch, codebooks, start_idx, 1.f, no_k, no_p, seed, offset,
                        use_graph, codes_out, stream, guided, uncond, 1.f, &rp);
+}
+
+// Arms the next rqamd_rqt_sample / _masked / _guided / _rows call on the handle (include/rqamd.h): device pointers to (batch, H, W, D)
+// fp32 each, any of them NULL, all NULL disarms.  The armed call draws the codes of the unarmed one; its outputs are copied out of
+// the handle's workspace next to the codes, so no captured graph ever holds a caller's pointer.
+extern "C" int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* model_logp_out, float* model_logp_uncond_out) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: null handle");
+    h->arm = rqamd_rqt::LogpArm{draw_logp_out, model_logp_out, model_logp_uncond_out};
+    return RQAMD_OK;
 }
 
 extern "C" int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures) {

@@ -101,6 +101,10 @@ struct SampleArgs {
     const float* row_gscale;        // [rows], or null: gscale above for every row
     const uint64_t* row_seeds;      // [rows], or null: rng / seed above.  Non-null: row r draws with key row_seeds[r], Philox row field 0
                                     // and counter offset + slot (rng is ignored) -- the stream of row 0 of a call seeded with row_seeds[r]
+    // log-probability of the draw (rqamd_sample_logits_logp / rqamd_rqt_sample_logp): non-null selects the LOGP instantiations
+    // (rqt_sample_logp.hip), which also write log(probability of the drawn code in the distribution the draw was made from) to
+    // logp_out[row * out_stride + slot] -- addressed like `out`, no mirror; kept codes write nothing.  Same codes as with null.
+    float* logp_out;
 };
 
 int rq_launch_guide_logits(const float* c, const float* u, int rows, int V, float scale, float* out, hipStream_t s);
@@ -204,6 +208,10 @@ struct LogProbArgs {
     long row0;
     int t_per, t_stride, t_off;
     float* out;             // [rows]
+    // step form (pos non-null): target = targets[R * t_stride + slot] and the result goes to out[R * t_stride + slot], slot =
+    // *pos * slot_D + slot_d -- one launch of a sampling step, over all its rows, after the sampler has written the code
+    const int* pos;
+    int slot_D, slot_d;
 };
 int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s);
 

@@ -17,8 +17,9 @@ static __device__ __forceinline__ float rq_u01(uint32_t r) { return fmaf((float)
 // guided instantiations.  The guided kernels live in an object of their own because instantiating them next to the unguided ones
 // changes the code the compiler emits for sample_topk_kernel<false> (a module-level effect: register allocation of its top-k search),
 // and the unguided instruction stream is to stay as it is.  rqt_sample_rows.hip does the same with RQ_SAMPLE_ROWS_TU for the per-row
-// instantiations (ROWS = true, unguided and guided), for the same reason.
-#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU)
+// instantiations (ROWS = true, unguided and guided), for the same reason, and rqt_sample_logp.hip with RQ_SAMPLE_LOGP_TU for the
+// instantiations that also report the log-probability of the draw (LOGP = true, all four of the above).
+#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU)
 #define RQ_SAMPLE_ONLY_TU 1
 #endif
 #ifndef RQ_SAMPLE_ONLY_TU
@@ -1488,7 +1489,9 @@ static __device__ __forceinline__ void sample_store(const SampleArgs& p, int row
     if (GUIDED && p.out_mirror) p.out[o + p.out_mirror] = (int64_t)code;
 }
 
-template <bool GUIDED, bool ROWS = false>
+// LOGP (rqt_sample_logp.hip): the log of the probability the drawn code had in the distribution the draw was made from -- after
+// guidance, temperature, top-k, top-p and renormalisation -- goes to p.logp_out, addressed like p.out (no mirror).  <.., false>: as before.
+template <bool GUIDED, bool ROWS = false, bool LOGP = false>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1673,6 +1676,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
             if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
         if (besti >= V) besti = 0;
         sample_store<GUIDED>(p, row, slot, besti);
+        if (LOGP) p.logp_out[(long)row * p.out_stride + slot] = logf(sx[besti]);     // the probability the race used
     }
 }
 
@@ -1720,7 +1724,7 @@ static __device__ __forceinline__ int blk_count_pp(int wave_cnt, SmpShared& sh, 
 }
 
 // softmax -> top-p -> renormalise -> (probs_out) -> draw, on NV scaled logits per thread (absent entries: idx < 0)
-template <bool GUIDED, bool ROWS, int NV, typename IdxF>
+template <bool GUIDED, bool ROWS, bool LOGP, int NV, typename IdxF>
 static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&q)[NV], IdxF idx_of, int row, SmpShared& sh) {
     const int tid = threadIdx.x, V = p.V;
     const float NEG_INF = -__int_as_float(0x7f800000);
@@ -1821,6 +1825,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
     const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     float best = -1.f;
     int besti = 0x7fffffff;
+    float bestq = 0.f;                                  // LOGP: the winner's own probability, carried next to (best, besti)
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int i = idx_of(k);
@@ -1830,26 +1835,28 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
         const unsigned w = (i & 3) == 0 ? r[0] : (i & 3) == 1 ? r[1] : (i & 3) == 2 ? r[2] : r[3];
         const float u = rq_u01(w);
         const float sc = q[k] / (-logf(u));
-        if (sc > best || (sc == best && i < besti)) { best = sc; besti = i; }
+        if (sc > best || (sc == best && i < besti)) { best = sc; besti = i; if (LOGP) bestq = q[k]; }
     }
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const float ov = rq_shfl_xor(best, m);
         const int oi = rq_shfl_xor_i(besti, m);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        const float oq = LOGP ? rq_shfl_xor(bestq, m) : 0.f;
+        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; if (LOGP) bestq = oq; }
     }
-    if (lane == 0) { sh.red[wave] = best; sh.redi[wave] = besti; }
+    if (lane == 0) { sh.red[wave] = best; sh.redi[wave] = besti; if (LOGP) sh.red2[wave] = bestq; }    // (red2: idle since the top-p search)
     rq_syncthreads();
     if (tid == 0) {
         for (int w = 1; w < SMP_T / 64; ++w)
-            if (sh.red[w] > best || (sh.red[w] == best && sh.redi[w] < besti)) { best = sh.red[w]; besti = sh.redi[w]; }
+            if (sh.red[w] > best || (sh.red[w] == best && sh.redi[w] < besti)) { best = sh.red[w]; besti = sh.redi[w]; if (LOGP) bestq = sh.red2[w]; }
         if (besti >= V) besti = 0;
         sample_store<GUIDED>(p, row, slot, besti);
+        if (LOGP) p.logp_out[(long)row * p.out_stride + slot] = logf(bestq);
     }
 }
 
-template <bool GUIDED, bool ROWS = false>
+template <bool GUIDED, bool ROWS = false, bool LOGP = false>
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
@@ -1974,7 +1981,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
         qi[k] = s < total ? sh.idx[s] : -1;
     }
     rq_syncthreads();
-    sample_tail<GUIDED, ROWS, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
+    sample_tail<GUIDED, ROWS, LOGP, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
 }
 
 // Unfiltered draw (top_k covers the vocabulary, top_p >= 1: the reference's defaults, transformers.py:309-323):
@@ -1982,10 +1989,14 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
 // Gumbel_i = -log(-log u_i) from the same Philox counters as sample_kernel -- no max / sum reductions, no
 // LDS copy of the row, so occupancy is set by registers only (the general kernel holds V floats in LDS:
 // 2 workgroups per CU, 830 us per call at 4096 x 16384; this one is bound by reading the logits once).
-template <bool GUIDED, bool ROWS = false>
+// LOGP: the streaming pass has no normalisation, so each thread also keeps a running (max, sum of exp) over its scrubbed, scaled values
+// -- the `take` of log_prob_kernel, one rescale per new maximum -- and the winner's own value; the four wavefronts combine them and
+// thread 0 writes x_best - M - logf(S).  expf / logf here, not the one-instruction forms: the result is not rounded to 16 bits afterwards.
+template <bool GUIDED, bool ROWS = false, bool LOGP = false>
 __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
+    __shared__ float redx[LOGP ? 4 : 1];
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (ROWS) {
@@ -2001,6 +2012,7 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     const float NEG_INF = -__int_as_float(0x7f800000);
     float best = NEG_INF;
     int besti = 0x7fffffff;
+    float bestx = NEG_INF, lm = NEG_INF, lsum = 0.f;    // LOGP: the winner's x, running maximum and sum of exp(x - lm)
     const bool vec = (V & 3) == 0;
     for (int i4 = tid; i4 * 4 < V; i4 += 256) {
         float v[4];
@@ -2033,61 +2045,75 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
             float x = v[e] * inv_t;
             if (x != x) x = NEG_INF;                                            // NaN scrub (utils.py:103-105)
             const float sc = x - __logf(-__logf(u));
-            if (i < V && sc > best) { best = sc; besti = i; }
+            if (i < V && sc > best) { best = sc; besti = i; if (LOGP) bestx = x; }
+            if (LOGP && i < V) {
+                if (x > lm) { lsum = lsum * expf(lm - x) + 1.0f; lm = x; }          // (first finite value: exp(-inf) = 0)
+                else if (!(x <= NEG_INF)) lsum += expf(x - lm);                     // (-inf adds nothing)
+            }
         }
+    }
+    float M = 0.f, S = 0.f;
+    if (LOGP) {
+        M = blk_max(lm, red);
+        S = blk_sum(lm > NEG_INF ? lsum * expf(lm - M) : 0.f, red);
     }
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const float ov = rq_shfl_xor(best, m);
         const int oi = rq_shfl_xor_i(besti, m);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        const float ox = LOGP ? rq_shfl_xor(bestx, m) : 0.f;
+        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; if (LOGP) bestx = ox; }
     }
-    if (lane == 0) { red[wave] = best; redi[wave] = besti; }
+    if (lane == 0) { red[wave] = best; redi[wave] = besti; if (LOGP) redx[wave] = bestx; }
     rq_syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
-            if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
+            if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; if (LOGP) bestx = redx[w]; }
         if (besti >= V) besti = 0;
         sample_store<GUIDED>(p, row, slot, besti);
+        if (LOGP) p.logp_out[(long)row * p.out_stride + slot] = (bestx - M) - logf(S);
     }
 }
 
 // the launch sequence of one sampling step, for the unguided (this object) or the guided kernels (rqt_sample_guided.hip)
-template <bool GUIDED>
+template <bool GUIDED, bool LOGP = false>
 static int launch_sample(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!(a.temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: temperature must be > 0");
     if (GUIDED && !(a.gscale - a.gscale == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: guidance scale must be finite");
     if ((a.top_k <= 0 || a.top_k >= a.V) && (a.top_p < 0.f || a.top_p >= 1.0f) && !a.probs_out && a.out) {
-        RQ_LAUNCH(sample_gumbel_kernel<GUIDED>, dim3(a.rows), dim3(256), 0, s, a);
+        const auto kern = sample_gumbel_kernel<GUIDED, false, LOGP>;
+        RQ_LAUNCH(kern, dim3(a.rows), dim3(256), 0, s, a);
         return rq_check_launch("sample_gumbel_kernel");
     }
     const size_t smem = (size_t)a.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)sample_kernel<GUIDED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)sample_kernel<GUIDED, false, LOGP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     SampleArgs b = a;
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch
     if (a.top_k > 0 && a.top_k < a.V && a.V <= SMP_T * SMP_VPT && a.V % 4 == 0 && a.redo && !env_lds_only) {
         // top-k on: register-resident kernel; rows it cannot finish (more than SMP_CAP keys tied into the top k, NaN
         // threshold) are flagged in a.redo and redone by the general kernel, whose other workgroups exit at once
-        RQ_LAUNCH(sample_topk_kernel<GUIDED>, dim3(a.rows), dim3(SMP_T), 0, s, a);
+        const auto kern = sample_topk_kernel<GUIDED, false, LOGP>;
+        RQ_LAUNCH(kern, dim3(a.rows), dim3(SMP_T), 0, s, a);
         RQ_TRY(rq_check_launch("sample_topk_kernel"));
     } else {
         b.redo = nullptr;
     }
-    RQ_LAUNCH(sample_kernel<GUIDED>, dim3(a.rows), dim3(SMP_T), smem, s, b);
+    const auto gen = sample_kernel<GUIDED, false, LOGP>;
+    RQ_LAUNCH(gen, dim3(a.rows), dim3(SMP_T), smem, s, b);
     return rq_check_launch("sample_kernel");
 }
 
-#ifdef RQ_SAMPLE_ROWS_TU
+#if defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU)
 // per-row parameters: the three kernels over all rows, each workgroup leaving at once unless the row is of its class (sample_row_class).
 // The streaming kernel cannot write probs_out and the register kernel needs V <= 16384, V % 4 == 0 and the redo workspace: where a
 // kernel can have no rows it is not launched.  The general kernel comes last (it reads the flags the register kernel wrote).  The
 // values are device arrays, so nothing about them is checked here; the kernels trap on none (temperature <= 0 or NaN draws garbage).
-template <bool GUIDED>
+template <bool GUIDED, bool LOGP = false>
 static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!a.row_top_k || !a.row_top_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: per-row top_k / top_p missing");
@@ -2095,17 +2121,17 @@ static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch, as in launch_sample
     if (env_lds_only) b.redo = nullptr;
     if (!b.probs_out && b.out) {
-        const auto kern = sample_gumbel_kernel<GUIDED, true>;
+        const auto kern = sample_gumbel_kernel<GUIDED, true, LOGP>;
         RQ_LAUNCH(kern, dim3(b.rows), dim3(256), 0, s, b);
         RQ_TRY(rq_check_launch("sample_gumbel_kernel (per row)"));
     }
     if (b.V <= SMP_T * SMP_VPT && b.V % 4 == 0 && b.redo) {
-        const auto kern = sample_topk_kernel<GUIDED, true>;
+        const auto kern = sample_topk_kernel<GUIDED, true, LOGP>;
         RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), 0, s, b);
         RQ_TRY(rq_check_launch("sample_topk_kernel (per row)"));
     }
     const size_t smem = (size_t)b.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
-    const auto kern = sample_kernel<GUIDED, true>;
+    const auto kern = sample_kernel<GUIDED, true, LOGP>;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2113,15 +2139,25 @@ static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), smem, s, b);
     return rq_check_launch("sample_kernel (per row)");
 }
+#endif
+#ifdef RQ_SAMPLE_ROWS_TU
 int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     return a.logits_u ? launch_sample_per_row<true>(a, s) : launch_sample_per_row<false>(a, s);
+}
+#elif defined(RQ_SAMPLE_LOGP_TU)
+// a.logp_out non-null: the LOGP instantiation of whichever of the four forms the arguments ask for; the class choice is theirs
+int rq_launch_sample_logp(const SampleArgs& a, hipStream_t s) {
+    if (a.row_temperature) return a.logits_u ? launch_sample_per_row<true, true>(a, s) : launch_sample_per_row<false, true>(a, s);
+    return a.logits_u ? launch_sample<true, true>(a, s) : launch_sample<false, true>(a, s);
 }
 #elif defined(RQ_SAMPLE_GUIDED_TU)
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s) { return launch_sample<true>(a, s); }
 #else
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s);     // rqt_sample_guided.hip
 int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s);    // rqt_sample_rows.hip
+int rq_launch_sample_logp(const SampleArgs& a, hipStream_t s);       // rqt_sample_logp.hip
 int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+    if (a.logp_out) return rq_launch_sample_logp(a, s);
     if (a.row_temperature) return rq_launch_sample_per_row(a, s);
     return a.logits_u ? rq_launch_sample_guided(a, s) : launch_sample<false>(a, s);
 }
@@ -2189,6 +2225,31 @@ extern "C" int rqamd_sample_logits_rows(const float* logits, int rows, int vocab
     a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.probs_out = probs_out; a.D = 1;
     a.redo = row_flags;
     a.row_temperature = temperature; a.row_top_k = top_k; a.row_top_p = top_p; a.row_seeds = seeds;
+    return rq_launch_sample(a, (hipStream_t)stream);
+}
+
+// the draw and its log-probability (include/rqamd.h): every LOGP instantiation at the caller's vocabulary size, without an engine.
+// logits_u null: unguided; row_temperature null: the scalar kernels with the scalars, else the per-row kernels with the arrays
+extern "C" int rqamd_sample_logits_logp(const float* logits, const float* logits_u, int rows, int vocab, float temperature, int top_k,
+                                        float top_p, float guidance_scale, const float* row_temperature, const int* row_top_k,
+                                        const float* row_top_p, const float* row_gscale, const uint64_t* row_seeds, uint64_t seed,
+                                        uint64_t offset, int64_t* samples_out, float* draw_logp_out, int* row_flags, void* stream) {
+    if (!logits || rows < 0 || !samples_out || !draw_logp_out)
+        return rq_fail(RQAMD_ERR_INVALID, "sample_logits_logp: bad argument (null logits, samples_out or draw_logp_out, or rows < 0)");
+    if (row_temperature && (!row_top_k || !row_top_p)) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_logp: row_temperature without row_top_k / row_top_p (null)");
+    if (!row_temperature && (row_top_k || row_top_p || row_gscale || row_seeds))
+        return rq_fail(RQAMD_ERR_INVALID, "sample_logits_logp: per-row arrays without row_temperature (null)");
+    if (row_gscale && !logits_u) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_logp: row_gscale without logits_u (null)");
+    if (rows == 0) return RQAMD_OK;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = vocab; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
+    a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.D = 1; a.redo = row_flags;
+    a.logits_u = logits_u; a.gscale = logits_u ? guidance_scale : 1.0f;
+    if (row_temperature) {
+        a.temperature = 1.0f; a.top_k = 0; a.top_p = -1.0f;
+        a.row_temperature = row_temperature; a.row_top_k = row_top_k; a.row_top_p = row_top_p; a.row_gscale = row_gscale; a.row_seeds = row_seeds;
+    }
+    a.logp_out = draw_logp_out;
     return rq_launch_sample(a, (hipStream_t)stream);
 }
 
@@ -2416,6 +2477,9 @@ int rq_launch_attn_packed(const AttnPackedArgs& a, hipStream_t s) {
 // row -- 16-byte loads when the row allows, one rescale per new maximum -- the four wavefronts combine through wave reductions and
 // eight floats of LDS, and thread 0 writes logit[target] - max - log(sum).  fp32 throughout (expf / logf, not the one-instruction
 // forms: the result is not rounded to 16 bits afterwards).
+// STEP (p.pos non-null; the model log-probabilities of an armed sampling call, after the sampler of the step): target and result sit
+// at slot *pos * slot_D + slot_d of their row, the position read from the device counter like every other launch of the step.
+template <bool STEP>
 __global__ __launch_bounds__(SMP_T) void log_prob_kernel(LogProbArgs p) {
     __shared__ float red[8];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -2438,14 +2502,16 @@ __global__ __launch_bounds__(SMP_T) void log_prob_kernel(LogProbArgs p) {
     const float S = blk_sum(m > NEG_INF ? sum * expf(m - M) : 0.f, red);
     if (tid == 0) {
         const long R = p.row0 + row;
-        const long tg = p.targets[(R / p.t_per) * p.t_stride + R % p.t_per + p.t_off];
-        p.out[row] = (tg >= 0 && tg < p.V) ? (lg[tg] - M) - logf(S) : __int_as_float(0x7fc00000);
+        const long at = STEP ? R * p.t_stride + ((long)(*p.pos) * p.slot_D + p.slot_d) : (R / p.t_per) * p.t_stride + R % p.t_per + p.t_off;
+        const long tg = p.targets[at];
+        p.out[STEP ? at : row] = (tg >= 0 && tg < p.V) ? (lg[tg] - M) - logf(S) : __int_as_float(0x7fc00000);
     }
 }
 int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
     if (a.rows < 1) return RQAMD_OK;
     if (a.V < 1 || a.t_per < 1) return rq_fail(RQAMD_ERR_INVALID, "log_prob: V = %d, t_per = %d", a.V, a.t_per);
-    RQ_LAUNCH(log_prob_kernel, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
+    if (a.pos) RQ_LAUNCH(log_prob_kernel<true>, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
+    else RQ_LAUNCH(log_prob_kernel<false>, dim3((unsigned)a.rows), dim3(SMP_T), 0, s, a);
     return rq_check_launch("log_prob_kernel");
 }
 

@@ -65,6 +65,9 @@ _SIGS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_sample_logits_rows': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_sample_logits_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     'rqamd_vae_create': (C.c_int, [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]),
     'rqamd_vae_destroy': (C.c_int, [C.c_void_p]),
     'rqamd_vae_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
@@ -89,6 +92,7 @@ _SIGS = {
                                         C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
                                         C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -387,6 +391,32 @@ def sample_logits_rows(logits, temperature, top_k, top_p, seeds=None, seed=0, of
                                              int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(samples), ptr(probs),
                                              ptr(flags), stream_of(logits)))
     return samples, probs
+
+
+def sample_logits_logp(logits, logits_u=None, temperature=1.0, top_k=None, top_p=None, guidance_scale=1.0, row_temperature=None,
+                       row_top_k=None, row_top_p=None, row_gscale=None, row_seeds=None, seed=0, offset=0, want_flags=True):
+    """rqamd_sample_logits_logp: one draw per row and the log of its probability in the distribution it was drawn from.  logits (and
+    logits_u, or None: unguided) (rows, vocab) fp32.  row_temperature None: the scalar form of sample_logits with temperature / top_k /
+    top_p (/ guidance_scale); else the per-row form of sample_logits_rows with the device tensors row_temperature (rows,) float32,
+    row_top_k (rows,) int32, row_top_p (rows,) float32 and, each or None, row_gscale (rows,) float32 and row_seeds (rows,) int64.
+    want_flags False: no row_flags workspace (every filtered row takes the general kernel).  -> (samples (rows,) int64, draw (rows,) fp32)"""
+    rows, vocab = logits.shape
+    if logits_u is not None and tuple(logits_u.shape) != (rows, vocab):
+        raise ValueError(f'sample_logits_logp: logits_u of shape {tuple(logits_u.shape)}; expected {(rows, vocab)}')
+    for name, t, dt in (('row_temperature', row_temperature, torch.float32), ('row_top_k', row_top_k, torch.int32),
+                        ('row_top_p', row_top_p, torch.float32), ('row_gscale', row_gscale, torch.float32), ('row_seeds', row_seeds, torch.int64)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (rows,) or t.dtype != dt or t.device != logits.device):
+            raise ValueError(f'sample_logits_logp: {name} must be a ({rows},) {dt} tensor on {logits.device}')
+    samples = torch.empty((rows,), dtype=torch.int64, device=logits.device)
+    draw = torch.empty((rows,), dtype=torch.float32, device=logits.device)
+    flags = torch.empty((max(rows, 1),), dtype=torch.int32, device=logits.device) if want_flags else None
+    with on_device_of(logits):
+        check(lib().rqamd_sample_logits_logp(ptr(logits, torch.float32), ptr(logits_u, torch.float32), rows, vocab, float(temperature),
+                                             0 if top_k is None else int(top_k), -1.0 if top_p is None else float(top_p),
+                                             float(guidance_scale), ptr(row_temperature), ptr(row_top_k), ptr(row_top_p), ptr(row_gscale),
+                                             ptr(row_seeds), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(samples), ptr(draw),
+                                             ptr(flags), stream_of(logits)))
+    return samples, draw
 
 
 def guide_logits(c, u, scale):
@@ -691,19 +721,34 @@ class RqtEngine(_Engine):
                     raise ValueError(f'codebook of shape {tuple(cb.shape)}; expected (>= {c.vocab_sizes[d]}, {c.input_embed_dim})')
         self._on_my_device(codes, cond, *codebooks[:c.D])
 
-    def sample(self, partial, cond, codebooks, start_loc, temperature, top_k, top_p, seed, offset, use_graph):
+    def _sample_call(self, partial, call, want_logp, guided=False):
+        """one sampling call; want_logp: armed through rqamd_rqt_sample_logp first (inside the same attempt: a failed call consumes the
+        arming) -> (draw, model, model_uncond or None), (B,H,W,D) fp32 each, else None"""
+        if not want_logp:
+            self._run(call)
+            return None
+        draw, model = (torch.empty(partial.shape, dtype=torch.float32, device=partial.device) for _ in range(2))
+        model_u = torch.empty_like(model) if guided else None
+
+        def armed():
+            rc = self._L.rqamd_rqt_sample_logp(self._h, ptr(draw), ptr(model), ptr(model_u))
+            return rc if rc != 0 else call()
+        self._run(armed)
+        return draw, model, model_u
+
+    def sample(self, partial, cond, codebooks, start_loc, temperature, top_k, top_p, seed, offset, use_graph, want_logp=False):
+        """want_logp (here and in the three forms below): also return (draw, model, model_uncond) of rqamd_rqt_sample_logp"""
         self._check(partial, cond, codebooks)
         B = partial.shape[0]
         out = torch.empty_like(partial)
         D = self.cfg.D
         cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
-        self._run(lambda: self._L.rqamd_rqt_sample(self._h, ptr(partial, torch.int64), ptr(cond, torch.int64), B, cbs,
-                                                 int(start_loc[0]), int(start_loc[1]), float(temperature), tk, tp,
-                                                 int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(bool(use_graph)),
-                                                 ptr(out), stream_of(partial)))
-        return out
+        lp = self._sample_call(partial, lambda: self._L.rqamd_rqt_sample(
+            self._h, ptr(partial, torch.int64), ptr(cond, torch.int64), B, cbs, int(start_loc[0]), int(start_loc[1]), float(temperature), tk, tp,
+            int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)), want_logp)
+        return (out, lp) if want_logp else out
 
-    def sample_masked(self, partial, keep, pos_active, cond, codebooks, temperature, top_k, top_p, seed, offset, use_graph):
+    def sample_masked(self, partial, keep, pos_active, cond, codebooks, temperature, top_k, top_p, seed, offset, use_graph, want_logp=False):
         """rqamd_rqt_sample_masked: `keep` (B,H,W,D) uint8 on the engine's device, nonzero = the code of `partial` is kept; `pos_active`
         a host sequence of H * W flags (0: every code of the position is kept in every row -- the caller's promise) or None."""
         self._check(partial, cond, codebooks)
@@ -724,13 +769,13 @@ class RqtEngine(_Engine):
         out = torch.empty_like(partial)
         D = c.D
         cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
-        self._run(lambda: self._L.rqamd_rqt_sample_masked(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), B, cbs,
-                                                        float(temperature), tk, tp, int(seed) & (2 ** 64 - 1),
-                                                        int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
-        return out
+        lp = self._sample_call(partial, lambda: self._L.rqamd_rqt_sample_masked(
+            self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), B, cbs, float(temperature), tk, tp, int(seed) & (2 ** 64 - 1),
+            int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)), want_logp)
+        return (out, lp) if want_logp else out
 
     def sample_guided(self, partial, keep, pos_active, cond, uncond, codebooks, start_loc, temperature, guidance_scale, top_k, top_p,
-                      seed, offset, use_graph):
+                      seed, offset, use_graph, want_logp=False):
         """rqamd_rqt_sample_guided: classifier-free guidance over the B images of `partial` (2B engine rows; rows B.. conditioned on
         `uncond`, None = zeros as for `cond`).  `keep` / `pos_active` as in sample_masked, or None: nothing kept."""
         self._check(partial, cond, codebooks)
@@ -757,14 +802,14 @@ class RqtEngine(_Engine):
         out = torch.empty_like(partial)
         D = c.D
         cbs, tk, tp = _ptr_array(codebooks[:D]), _int_array(top_k[:D]), (C.c_float * D)(*[float(p) for p in top_p[:D]])
-        self._run(lambda: self._L.rqamd_rqt_sample_guided(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64),
-                                                        ptr(uncond, torch.int64), B, cbs, int(start_loc[0]), int(start_loc[1]),
-                                                        float(temperature), float(guidance_scale), tk, tp, int(seed) & (2 ** 64 - 1),
-                                                        int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out), stream_of(partial)))
-        return out
+        lp = self._sample_call(partial, lambda: self._L.rqamd_rqt_sample_guided(
+            self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), ptr(uncond, torch.int64), B, cbs, int(start_loc[0]),
+            int(start_loc[1]), float(temperature), float(guidance_scale), tk, tp, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+            int(bool(use_graph)), ptr(out), stream_of(partial)), want_logp, guided=True)
+        return (out, lp) if want_logp else out
 
     def sample_rows(self, partial, keep, pos_active, cond, uncond, codebooks, start_loc, temperature, top_k, top_p, guidance_scale,
-                    seeds, seed, offset, use_graph):
+                    seeds, seed, offset, use_graph, want_logp=False):
         """rqamd_rqt_sample_rows: sampling parameters per image.  temperature (B,), top_k (B, D), top_p (B, D), guidance_scale (B,) or
         None (with uncond None: unguided) and seeds (B,) or None are HOST sequences (nested for the two (B, D) tables); `keep` /
         `pos_active` as in sample_masked or None, `uncond` as in sample_guided.  Image b is drawn as the scalar entry point draws row
@@ -809,11 +854,11 @@ class RqtEngine(_Engine):
         aT, ak, ap = (C.c_float * B)(*T), (C.c_int * (B * D))(*tk), (C.c_float * (B * D))(*tp)
         ag = None if gs is None else (C.c_float * B)(*gs)
         asd = None if sd is None else (C.c_uint64 * B)(*sd)
-        self._run(lambda: self._L.rqamd_rqt_sample_rows(self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64),
-                                                      ptr(uncond, torch.int64), B, cbs, int(start_loc[0]), int(start_loc[1]), aT, ak, ap,
-                                                      ag, asd, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                                      int(bool(use_graph)), ptr(out), stream_of(partial)))
-        return out
+        lp = self._sample_call(partial, lambda: self._L.rqamd_rqt_sample_rows(
+            self._h, ptr(partial, torch.int64), kp, pa, ptr(cond, torch.int64), ptr(uncond, torch.int64), B, cbs, int(start_loc[0]),
+            int(start_loc[1]), aT, ak, ap, ag, asd, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(bool(use_graph)), ptr(out),
+            stream_of(partial)), want_logp, guided=gs is not None)
+        return (out, lp) if want_logp else out
 
     def graph_captures(self):
         """position graphs this handle has captured so far (rqamd_rqt_graph_captures); a call that only replays leaves it unchanged"""

@@ -57,6 +57,11 @@ class SideStream:
         with torch.cuda.stream(side):
             out = fn()
         cur.wait_stream(side)
-        for t in (out if isinstance(out, tuple) else (out,)):
-            t.record_stream(cur)
+        def tag(o):                                   # (tuples may nest and hold None: sample(return_log_probs=True))
+            if isinstance(o, tuple):
+                for t in o:
+                    tag(t)
+            elif o is not None:
+                o.record_stream(cur)
+        tag(out)
         return out

@@ -1,5 +1,5 @@
 """rqvae/models/rqtransformer/__init__.py of the reference."""
-from .transformers import RQTransformer
+from .transformers import RQTransformer, SampleLogProbs
 
 
 def get_rqtransformer(config):

@@ -15,7 +15,7 @@ whole loop is one asynchronous C call) and ``fast`` is unused by the reference i
 import contextlib
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 import torch.nn as nn
@@ -39,6 +39,12 @@ class _AttrView(dict):
 
 def _attr(d):
     return _AttrView({k: _attr(v) if isinstance(v, dict) else v for k, v in d.items()})
+
+
+# sample(return_log_probs=True) / sample_guided(...): (B,H,W,D) fp32 each.  draw: log-probability of every drawn code in the distribution
+# it was drawn from (after guidance, temperature, top-k, top-p, renormalisation), +0.0 for kept codes; model: log_softmax of the raw
+# conditional logits at the code, NaN where the head did not run; model_uncond: the same under `uncond` (None when unguided)
+SampleLogProbs = namedtuple('SampleLogProbs', ['draw', 'model', 'model_uncond'])
 
 
 class RQTransformer(Stage2Model):
@@ -102,6 +108,7 @@ class RQTransformer(Stage2Model):
         # launch; 'one_pass' (or RQAMD_FORWARD=one_pass): every position at once, no KV cache (rqamd_rqt_forward_onepass) -- same
         # arithmetic, other GEMM tiles.  cached_forward and sample (cached or not) always step.
         self.forward_mode = os.environ.get('RQAMD_FORWARD', 'stepped')
+        self._return_log_probs = False                   # inside `with self.return_log_probs()`: sample() also returns SampleLogProbs
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
 
     # ------------------------------------------------------------------ engine plumbing
@@ -310,13 +317,16 @@ class RQTransformer(Stage2Model):
         give every image its own values (numbers and lists keep the reference's meaning: one value, or one per depth, for every
         image; arguments not given as tensors are broadcast).  Image b is drawn exactly as a call with b's values as scalars draws
         row b, whatever the other images ask for, and one set of captured graphs serves every setting.  Inside ``with
-        self.seeds(s)`` image b draws from the Philox stream of seed s[b] instead of the device generator (see seeds())."""
+        self.seeds(s)`` image b draws from the Philox stream of seed s[b] instead of the device generator (see seeds()).
+        Inside ``with self.return_log_probs():`` the call returns ``(codes, SampleLogProbs(draw, model, None))`` -- the codes are those
+        of the plain call (see return_log_probs())."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        want = self._want_log_probs(cached)
         rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p)
         if rows is not None:
-            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask)
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, want_logp=want)
         top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
@@ -339,11 +349,44 @@ class RQTransformer(Stage2Model):
         if keep is not None:
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
-            return self._on_side_stream(device, lambda: eng.sample_masked(xs, keep8, pos_active, c, cbs, temperature, top_k_list,
-                                                                          top_p_list, seed, offset, self.use_graph))
+            return self._with_log_probs(want, self._on_side_stream(device, lambda: eng.sample_masked(
+                xs, keep8, pos_active, c, cbs, temperature, top_k_list, top_p_list, seed, offset, self.use_graph, **want)))
         out = self._on_side_stream(device, lambda: eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list,
-                                                              seed, offset, self.use_graph))
-        return out
+                                                              seed, offset, self.use_graph, **want))
+        return self._with_log_probs(want, out)
+
+    @contextlib.contextmanager
+    def return_log_probs(self, on=True):
+        """Log-probabilities of the draws (not in the reference).  The sample() / sample_guided() calls made inside the block return
+        ``(codes, SampleLogProbs(draw, model, model_uncond))`` instead of ``codes``; the codes are bit for bit those of the same call
+        outside the block.  (B,H,W,D) fp32 each: ``draw`` the log of the probability the drawn code had in the distribution it was
+        drawn from (logits after guidance, temperature, top-k, top-p and renormalisation; +0.0 for kept codes and codes before
+        start_loc), ``model`` log_softmax of the image's raw conditional logits at the code (kept codes included; NaN where no head
+        ran: before start_loc, fully kept positions), ``model_uncond`` the same under `uncond` (None for sample()).  Works with scalar
+        and per-image parameters, seeds(), keep_mask, start_loc, amp and use_graph on or off; the host loops (``sampler='torch'``,
+        ``cached=False``) return codes only and raise NotImplementedError inside the block.  (A context rather than an argument, like
+        seeds() and for its reason: the argument lists of sample() and sample_guided() stay as they are.)"""
+        saved, self._return_log_probs = self._return_log_probs, bool(on)
+        try:
+            yield self
+        finally:
+            self._return_log_probs = saved
+
+    def _want_log_probs(self, cached):
+        """keyword arguments of the engine's sampling calls inside return_log_probs() (none outside); the host loops have no such path"""
+        if not self._return_log_probs:
+            return {}
+        if self.sampler == 'torch' or not cached:
+            raise NotImplementedError("return_log_probs() needs the engine's own sampling loop: log-probabilities are not available with "
+                                      "sampler='torch' or cached=False (the host loops return codes only)")
+        return dict(want_logp=True)
+
+    @staticmethod
+    def _with_log_probs(want, result):
+        if not want:
+            return result
+        codes, lp = result
+        return codes, SampleLogProbs(*lp)
 
     def _filter_lists(self, top_k, top_p):
         """top_k / top_p of sample() -> one value per depth (transformers.py:309-323)"""
@@ -461,7 +504,8 @@ class RQTransformer(Stage2Model):
             out[idx] = _native.guide_logits(c[idx].contiguous(), u[idx].contiguous(), s)
         return out
 
-    def _sample_per_image(self, rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, guided=False, uncond=None):
+    def _sample_per_image(self, rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, guided=False, uncond=None,
+                          want_logp={}):
         """sample() / sample_guided() with per-image parameters: rqamd_rqt_sample_rows, or the two host loops over sample_logits_rows"""
         (H, W, D) = self.block_size
         B = partial_sample.shape[0]
@@ -499,9 +543,9 @@ class RQTransformer(Stage2Model):
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
             start = (0, 0)                                                   # (the kept prefix is part of `keep`)
-        return self._on_side_stream(device, lambda: eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'],
-                                                                    rows['gs'] if guided else None, rows['seeds'], seed, offset,
-                                                                    self.use_graph))
+        return self._with_log_probs(want_logp, self._on_side_stream(device, lambda: eng.sample_rows(
+            xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None, rows['seeds'], seed,
+            offset, self.use_graph, **want_logp)))
 
     @torch.no_grad()
     def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
@@ -514,13 +558,16 @@ class RQTransformer(Stage2Model):
         conditional twin drew, and row b uses the temperature, top-k, top-p and Philox counter of row b of sample().  Returns
         (B,H,W,D) int64.  ``keep_mask`` composes as in sample(); ``cached=False`` and ``sampler='torch'`` are the host loops of
         sample() over the 2B rows, the former bit for bit equal to ``cached=True``.  Per-image ``temperature`` / ``top_k`` / ``top_p``
-        tensors and ``with self.seeds(...)`` as in sample(); ``guidance_scale`` as a (B,) tensor gives every image its own scale."""
+        tensors and ``with self.seeds(...)`` as in sample(); ``guidance_scale`` as a (B,) tensor gives every image its own scale.
+        Inside ``with self.return_log_probs():`` the call returns ``(codes, SampleLogProbs(draw, model, model_uncond))``, draw under the
+        guided distribution, model / model_uncond under the raw logits of the two twins."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        want = self._want_log_probs(cached)
         rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, guidance_scale)
         if rows is not None:
-            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, True, uncond)
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, True, uncond, want_logp=want)
         if not math.isfinite(float(guidance_scale)):
             raise ValueError(f'guidance_scale {guidance_scale} is not finite')
         scale = float(guidance_scale)
@@ -555,8 +602,8 @@ class RQTransformer(Stage2Model):
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
             start = (0, 0)                                                   # (the kept prefix is part of `keep`)
-        return self._on_side_stream(device, lambda: eng.sample_guided(xs, keep8, pos_active, c, u, cbs, start, temperature, scale,
-                                                                      top_k_list, top_p_list, seed, offset, self.use_graph))
+        return self._with_log_probs(want, self._on_side_stream(device, lambda: eng.sample_guided(
+            xs, keep8, pos_active, c, u, cbs, start, temperature, scale, top_k_list, top_p_list, seed, offset, self.use_graph, **want)))
 
     def _keep_flags(self, keep_mask, xs, start_loc):
         """keep_mask of sample() -> (keep (B,H,W,D) bool on the device of `xs`, active (H*W, D) bool on the host: some row draws that
