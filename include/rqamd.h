@@ -115,6 +115,12 @@ int rqamd_rq_embed(const int64_t* codes, const float* const* codebooks, const in
 int rqamd_sample_logits(const float* logits, int rows, int vocab, float temperature, int top_k,
                         float top_p, uint64_t seed, uint64_t offset, int64_t* samples_out,
                         float* probs_out, int* row_flags, void* stream);
+/* rqamd_soft_ce <- soft_target_cross_entropy(reduction='none') (rqvae/optimizer/loss.py:68-84) over `rows` rows (additive, ABI v7):
+ * loss_out[r] = sum_v -t_v (x_v - m - log(sum_v exp(x_v - m) + 1e-7)), m = max_v x_v, x = logits[r * ld_logits + v], t = targets[r *
+ * ld_targets + v], fp32 throughout.  The targets need not sum to 1; an all-zero row gives 0.  Non-finite logits behave as there: a NaN
+ * logit, or -inf under a zero target (0 * -inf), makes the row NaN; -inf under a positive target gives +inf. */
+int rqamd_soft_ce(const float* logits, int64_t ld_logits, const float* targets, int64_t ld_targets, int64_t rows, int vocab,
+                  float* loss_out, void* stream);
 /* rqamd_sample_logits with a temperature, top-k and top-p per row (not in the reference); additive, ABI v7.  temperature, top_k,
  * top_p: DEVICE arrays of `rows` entries; seeds: a device array of `rows` Philox keys, or NULL.  Row r is filtered and drawn exactly
  * as row r of rqamd_sample_logits(logits, rows, vocab, temperature[r], top_k[r], top_p[r], seed, offset, ...) over the same matrix
@@ -312,6 +318,20 @@ int rqamd_rqt_forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t*
  * needs cond).  A code outside 0..vocab-1 gives NaN. */
 int rqamd_rqt_log_probs(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch,
                         const float* const* codebooks, float* logp_out, float* cond_logp_out, void* stream);
+/* Soft-target cross entropy of every code under the same pass (additive, ABI v7): loss_out (batch,H,W,D) fp32 =
+ * soft_target_cross_entropy(logits, soft targets, reduction='none') (rqvae/optimizer/loss.py:68-84), what compute_loss /
+ * compute_codebook_loss (transformers.py:371-410) average with use_soft_target -- reduced from the sub-chunks of logits rows
+ * rqamd_rqt_log_probs uses (rqamd_rqt_set_option "fwd.logits_bytes", default 48 << 20, at least one depth group), so
+ * (batch,H,W,D,vocab) logits never exist.  Exactly one of
+ *   soft_targets (batch,H,W,D,vocab) fp32: the soft codes of RQBottleneck.get_soft_codes (quantizations.py:371-400), or any weights;
+ *   z (batch,H,W,input_embed_dim) fp32: the features the codes were quantised from, with code_norms[d] (vocab) from
+ *     rqamd_rq_code_norms and temp > 0 -- the targets softmax(-distance(residual_d, codebook_d) / temp) are formed per sub-chunk
+ *     from the residual of the GIVEN codes (argmin or drawn) and never stored; codebooks[d] must hold exactly `vocab` codes.
+ * All depths must share one vocabulary (RQAMD_ERR_UNSUPPORTED otherwise); with z, input_embed_dim is 64, 128, 192 or 256.
+ * cond_logp_out: as rqamd_rqt_log_probs. */
+int rqamd_rqt_soft_loss(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch, const float* const* codebooks,
+                        const float* soft_targets, const float* z, const float* const* code_norms, float temp, float* loss_out,
+                        float* cond_logp_out, void* stream);
 /* Stepping form of rqamd_rqt_sample for callers that draw the samples themselves -- e.g. torch.multinomial on the filtered
  * probabilities, which consumes the device generator exactly as the reference's sample_from_logits does
  * (rqvae/utils/utils.py:112; RQTransformer.sample transformers.py:346-364 is this loop):

@@ -135,6 +135,7 @@ struct rqamd_rqt {
     // one-pass teacher-forced forward (forward_onepass): a workspace of its own, sized by a row budget per chunk -- never h->ws / h->kv,
     // whose addresses the captured sampling graphs hold
     int fwd_chunk_rows = 4096;    // "fwd.chunk_rows": body rows per chunk of images, head rows per sub-chunk
+    int fwd_logits_bytes = 48 << 20;   // "fwd.logits_bytes": the logits sub-chunk the log_probs / soft_loss forms reduce (whole depth groups, at least one)
     DevBuf fws;
 };
 
@@ -281,6 +282,11 @@ extern "C" int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value) {
     if (strcmp(name, "fwd.chunk_rows") == 0) {   // row budget of the one-pass forward's chunks (tests force several chunks on a tiny model)
         if (value < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: fwd.chunk_rows = %d < 1", value);
         h->fwd_chunk_rows = value;
+        return RQAMD_OK;
+    }
+    if (strcmp(name, "fwd.logits_bytes") == 0) { // size of the logits sub-chunk of rqamd_rqt_log_probs / rqamd_rqt_soft_loss (tests force the classifier loop to split)
+        if (value < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: fwd.logits_bytes = %d < 1", value);
+        h->fwd_logits_bytes = value;
         return RQAMD_OK;
     }
     return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: unknown option '%s'", name);
@@ -1052,12 +1058,23 @@ extern "C" int rqamd_rqt_forward(rqamd_rqt* h, const int64_t* codes, const int64
 // positions within the same budget; the head rows' order IS the order of the logits, so the classifier writes into logits_out.
 // logp form: the classifier writes sub-chunks of rows into a workspace buffer of ~48 MB that log_prob_kernel reduces to one number
 // per row -- (B,H,W,D,V) never exists.  No KV cache is read, written or allocated, and h->ws / h->kv are not touched.
+// soft_loss form (rqamd_rqt_soft_loss): the same sub-chunks reduced to the soft-target cross entropy of each row, against the caller's
+// soft targets (soft_targets) or against softmax(-distance(residual, codebook) / temp) formed per sub-chunk from z (the features the codes
+// were quantised from): residual rows, one split-mode quantiser launch into a second buffer of the sub-chunk's size, soft_ce_pair_kernel.
 struct OnePassOut {
     float* logits;       // (B,HW,D,V) or null
     float* cond_logits;  // (B, cond_len-1, vocab_size_cond) or null
     float* logp;         // (B,HW,D) or null
     float* cond_logp;    // (B, cond_len-1) or null
+    float* soft_loss;    // (B,HW,D) or null
+    const float* soft_targets;          // (B,HW,D,V), or
+    const float* z;                     // (B,HW,Din) with code_norms[d] (V) and inv_temp
+    const float* const* code_norms;
+    float inv_temp;
 };
+
+int rq_launch_neg_distances(const float* x, const float* codebook, const float* code_norms, int n_embed, long n_vec, int dim, float inv_temp,
+                            float* logit_out, float* part_v, int* part_i, hipStream_t st);      // quantize.hip
 
 // the workspace pointers run_block works on, swapped for the duration of a one-pass call (restored on every exit path)
 struct WorkspaceSwap {
@@ -1085,18 +1102,22 @@ static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* co
     if (n_grp < 1) n_grp = 1;
     if (n_grp > (long)n_img * HW) n_grp = (long)n_img * HW;
     const size_t rb = (size_t)n_img * Tb, rh = (size_t)n_grp * D, rows = rb > rh ? rb : rh;
-    // logits sub-chunk of the logp forms: ~48 MB of fp32 rows, whole depth groups (BatchLinear runs one GEMM per depth over it)
-    long cls_grp = (long)((48u << 20) / ((size_t)V * 4)) / D;
+    // logits sub-chunk of the logp / soft_loss forms: fwd_logits_bytes (~48 MB) of fp32 rows, whole depth groups (BatchLinear runs one GEMM per depth over it)
+    long cls_grp = (long)((size_t)h->fwd_logits_bytes / ((size_t)V * 4)) / D;
     if (cls_grp < 1) cls_grp = 1;
     if (cls_grp > n_grp) cls_grp = n_grp;
-    long ccls_rows = (long)((48u << 20) / ((size_t)vc * 4));
+    long ccls_rows = (long)((size_t)h->fwd_logits_bytes / ((size_t)vc * 4));
     if (ccls_rows < 1) ccls_rows = 1;
     if (ccls_rows > (long)n_img * (P > 0 ? P : 1)) ccls_rows = (long)n_img * (P > 0 ? P : 1);
     size_t lg_bytes = 0;
-    if (o.logp) lg_bytes = (size_t)cls_grp * D * V * 4;
+    if (o.logp || o.soft_loss) lg_bytes = (size_t)cls_grp * D * V * 4;
     if (o.cond_logp && (size_t)ccls_rows * vc * 4 > lg_bytes) lg_bytes = (size_t)ccls_rows * vc * 4;
-    const size_t total = al(rb * E * 4) + al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
+    const size_t total_fwd = al(rb * E * 4) + al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
                          + al(rows * 4 * E * 2) + al(rows * h->Din * 2) + al(lg_bytes);
+    // soft_loss from z: target logits, residual rows and the quantiser's partial minima of one logits sub-chunk (cls_grp * D rows)
+    const size_t sub_rows = (size_t)cls_grp * D;
+    const size_t tl_bytes = o.z ? sub_rows * V * 4 : 0, rs_bytes = o.z ? sub_rows * h->Din * 4 : 0, pm_bytes = o.z ? sub_rows * 64 * 4 : 0;
+    const size_t total = total_fwd + al(tl_bytes) + al(rs_bytes) + 2 * al(pm_bytes);
     RQ_TRY(h->fws.reserve(total));
     WorkspaceSwap keep(h);
     char* p = (char*)h->fws.p;
@@ -1107,6 +1128,12 @@ static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* co
     h->qkv = (bf16_t*)take(rows * 3 * E * 2); h->hbuf = (bf16_t*)take(rows * 4 * E * 2);
     h->ain = (bf16_t*)take(rows * h->Din * 2);
     float* lg = (float*)take(lg_bytes);
+    float* tl = (float*)take(tl_bytes);
+    float* rs = (float*)take(rs_bytes);
+    float* pm_v = (float*)take(pm_bytes);
+    int* pm_i = (int*)take(pm_bytes);
+    bool one_cb = true;                            // a shared codebook: one quantiser launch over the rows of all depths
+    for (int d = 1; o.z && d < D; ++d) one_cb = one_cb && codebooks[d] == codebooks[0] && o.code_norms[d] == o.code_norms[0];
 
     for (int b0 = 0; b0 < B; b0 += n_img) {
         const int n = B - b0 < n_img ? B - b0 : n_img;
@@ -1212,6 +1239,27 @@ static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* co
                     lp.out = o.logp + row_g + c0 * D;
                     RQ_TRY(rq_launch_log_prob(lp, st));
                 }
+                if (o.soft_loss) {
+                    SoftCeArgs sc{};
+                    sc.logits = dst; sc.ld = V; sc.rows = (int)(cg * D); sc.V = V; sc.out = o.soft_loss + row_g + c0 * D;
+                    if (o.soft_targets) {
+                        sc.targets = o.soft_targets + (row_g + c0 * D) * V; sc.ldt = V;
+                    } else {
+                        ResidRowsArgs rr{};
+                        rr.z = o.z; rr.codes = codes; rr.vec0 = (long)b0 * HW + g0 + c0; rr.n_vec = cg; rr.D = D; rr.dim = h->Din; rr.out = rs;
+                        for (int d = 0; d < D; ++d) { rr.cb[d] = codebooks[d]; rr.K[d] = V; }
+                        RQ_TRY(rq_launch_resid_rows(rr, st));
+                        if (one_cb) {
+                            RQ_TRY(rq_launch_neg_distances(rs, codebooks[0], o.code_norms[0], V, cg * D, h->Din, o.inv_temp, tl, pm_v, pm_i, st));
+                        } else {
+                            for (int d = 0; d < D; ++d)
+                                RQ_TRY(rq_launch_neg_distances(rs + (size_t)d * cg * h->Din, codebooks[d], o.code_norms[d], V, cg, h->Din, o.inv_temp,
+                                                               tl + (size_t)d * cg * V, pm_v, pm_i, st));
+                        }
+                        sc.targets = tl; sc.ldt = V; sc.pair_D = D; sc.pair_nv = cg;
+                    }
+                    RQ_TRY(rq_launch_soft_ce(sc, st));
+                }
             }
         }
     }
@@ -1225,7 +1273,8 @@ extern "C" int rqamd_rqt_forward_onepass(rqamd_rqt* h, const int64_t* codes, con
     if (cond_logits_out && h->cond_len <= 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_forward_onepass: cond_logits need block_size_cond > 1");
     if (h->seen.size() - h->n_ccls_seen < h->n_required)
         return rq_fail(RQAMD_ERR_STATE, "rqt: only %zu of %zu parameters set", h->seen.size() - h->n_ccls_seen, h->n_required);
-    const OnePassOut o{logits_out, cond_logits_out, nullptr, nullptr};
+    OnePassOut o{};
+    o.logits = logits_out; o.cond_logits = cond_logits_out;
     return forward_onepass(h, codes, cond, batch, codebooks, o, (hipStream_t)stream);
 }
 
@@ -1237,7 +1286,37 @@ extern "C" int rqamd_rqt_log_probs(rqamd_rqt* h, const int64_t* codes, const int
     if (cond_logp_out && !cond) return rq_fail(RQAMD_ERR_INVALID, "rqt_log_probs: cond_logp_out without cond");
     if (h->seen.size() - h->n_ccls_seen < h->n_required)
         return rq_fail(RQAMD_ERR_STATE, "rqt: only %zu of %zu parameters set", h->seen.size() - h->n_ccls_seen, h->n_required);
-    const OnePassOut o{nullptr, nullptr, logp_out, cond_logp_out};
+    OnePassOut o{};
+    o.logp = logp_out; o.cond_logp = cond_logp_out;
+    return forward_onepass(h, codes, cond, batch, codebooks, o, (hipStream_t)stream);
+}
+
+// rqamd_rqt_soft_loss (include/rqamd.h): the soft-target cross entropy of every code under the same pass
+extern "C" int rqamd_rqt_soft_loss(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int batch, const float* const* codebooks,
+                                   const float* soft_targets, const float* z, const float* const* code_norms, float temp, float* loss_out,
+                                   float* cond_logp_out, void* stream) {
+    if (!h || !codes || !codebooks || !loss_out) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: null argument");
+    if (batch < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: batch < 1");
+    if ((soft_targets != nullptr) == (z != nullptr)) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: exactly one of soft_targets and z must be given");
+    if (cond_logp_out && h->cond_len <= 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: cond_logp needs block_size_cond > 1");
+    if (cond_logp_out && !cond) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: cond_logp_out without cond");
+    for (int d = 0; d < h->D; ++d)
+        if (h->Vd[d] != h->V)
+            return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_soft_loss: vocab_sizes[%d] = %d != %d: one vocabulary for all depths needed (the soft codes are concatenated along depth)",
+                           d, h->Vd[d], h->V);
+    OnePassOut o{};
+    o.soft_loss = loss_out; o.cond_logp = cond_logp_out; o.soft_targets = soft_targets;
+    if (z) {
+        if (!code_norms) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: z without code_norms");
+        for (int d = 0; d < h->D; ++d)
+            if (!codebooks[d] || !code_norms[d]) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: null codebook / code_norms[%d]", d);
+        if (!(temp > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_soft_loss: temp must be > 0");
+        if (h->Din % 64 != 0 || h->Din < 64 || h->Din > 256)
+            return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_soft_loss: input_embed_dim %d must be 64, 128, 192 or 256 to form the targets from z", h->Din);
+        o.z = z; o.code_norms = code_norms; o.inv_temp = 1.0f / temp;
+    }
+    if (h->seen.size() - h->n_ccls_seen < h->n_required)
+        return rq_fail(RQAMD_ERR_STATE, "rqt: only %zu of %zu parameters set", h->seen.size() - h->n_ccls_seen, h->n_required);
     return forward_onepass(h, codes, cond, batch, codebooks, o, (hipStream_t)stream);
 }
 

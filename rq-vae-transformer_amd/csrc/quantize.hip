@@ -555,31 +555,41 @@ extern "C" int rqamd_rq_soft_codes(const float* x, const float* const* codebooks
     return RQAMD_OK;
 }
 
+// the split-mode launch on its own: logit_out[v][k] = -distance(x_v, c_k) * inv_temp for ONE codebook (n_vec, K) -- inv_temp = -1: the
+// distance itself (-d * -1, exact).  part_v / part_i: n_vec * 64 floats / ints of scratch for the partial minima the kernel also writes.
+// Also called by the RQ-Transformer engine's soft-target loss (csrc/engine_rqt.hip), whose targets are softmax of these rows.
+int rq_launch_neg_distances(const float* x, const float* codebook, const float* code_norms, int n_embed, long n_vec, int dim, float inv_temp,
+                            float* logit_out, float* part_v, int* part_i, hipStream_t st) {
+    const long ntiles = (n_vec + QT_M - 1) / QT_M;
+    const int tiles_k = (n_embed + QT_N - 1) / QT_N;
+    int S = (int)(512 / ntiles);
+    S = S < 1 ? 1 : (S > 64 ? 64 : S);
+    S = S > tiles_k ? tiles_k : S;
+    RqQuantArgs a{};
+    a.cb[0] = codebook; a.K[0] = n_embed; a.cn[0] = code_norms;
+    a.depth = 1; a.dim = dim; a.n_vec = n_vec; a.codes = nullptr; a.quant_cum = nullptr; a.x = x; a.dep = 0;
+    a.part_v = part_v;
+    a.part_i = part_i;
+    a.logit_out = logit_out;
+    a.inv_temp = inv_temp;
+    a.tiles_per_split = (tiles_k + S - 1) / S;
+    a.n_split = (tiles_k + a.tiles_per_split - 1) / a.tiles_per_split;
+    return rq_launch_quant<1>(a, dim3((unsigned)ntiles, (unsigned)a.n_split), st);
+}
+
 // VQEmbedding.compute_distances (quantizations.py:43-62) as a stand-alone call: the split-mode kernel's logit output with
-// inv_temp = -1 is the distance itself (-d * -1, exact); the partial minima it also writes go to the workspace and are not used.
+// inv_temp = -1; the partial minima it also writes go to the workspace and are not used.
 extern "C" int rqamd_rq_distances(const float* x, const float* codebook, const float* code_norms, int n_embed, int64_t n_vec, int dim,
                                   float* dist_out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (n_vec == 0) return RQAMD_OK;
     if (!x || !codebook || !code_norms || !dist_out || !workspace) return rq_fail(RQAMD_ERR_INVALID, "rq_distances: null argument");
     if (dim % 64 != 0 || dim < 64 || dim > 256) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rq_distances: dim %d must be 64, 128, 192 or 256", dim);
     if (n_embed < 1) return rq_fail(RQAMD_ERR_INVALID, "rq_distances: empty codebook");
-    const long ntiles = (n_vec + QT_M - 1) / QT_M;
-    const int tiles_k = (n_embed + QT_N - 1) / QT_N;
-    int S = (int)(512 / ntiles);
-    S = S < 1 ? 1 : (S > 64 ? 64 : S);
-    S = S > tiles_k ? tiles_k : S;
     const size_t need = (size_t)n_vec * 64 * 8;
     if ((size_t)workspace_bytes < need) return rq_fail(RQAMD_ERR_INVALID, "rq_distances: workspace of %zu bytes needed", need);
-    RqQuantArgs a{};
-    a.cb[0] = codebook; a.K[0] = n_embed; a.cn[0] = code_norms;
-    a.depth = 1; a.dim = dim; a.n_vec = n_vec; a.codes = nullptr; a.quant_cum = nullptr; a.x = x; a.dep = 0;
-    a.part_v = (float*)workspace;
-    a.part_i = (int*)(a.part_v + (size_t)n_vec * 64);
-    a.logit_out = dist_out;
-    a.inv_temp = -1.0f;
-    a.tiles_per_split = (tiles_k + S - 1) / S;
-    a.n_split = (tiles_k + a.tiles_per_split - 1) / a.tiles_per_split;
-    return rq_launch_quant<1>(a, dim3((unsigned)ntiles, (unsigned)a.n_split), (hipStream_t)stream);
+    float* part_v = (float*)workspace;
+    return rq_launch_neg_distances(x, codebook, code_norms, n_embed, (long)n_vec, dim, -1.0f, dist_out, part_v,
+                                   (int*)(part_v + (size_t)n_vec * 64), (hipStream_t)stream);
 }
 
 extern "C" int rqamd_rq_embed(const int64_t* codes, const float* const* codebooks, const int* n_embed, int depth,

@@ -215,5 +215,34 @@ struct LogProbArgs {
 };
 int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s);
 
+// Soft-target cross entropy of logits rows (rqvae/optimizer/loss.py:68-76): out[r] = sum_v -t_v (x_v - m - log(sum exp(x - m) + 1e-7)),
+// m = max_v x_v, fp32.  Plain form (pair_D == 0): t = targets[r][:], any non-negative weights.  Pair form (pair_D > 0): `targets` holds
+// target LOGITS a, t = softmax(a) formed in the same pass; the rows of the two matrices pair up as logits row r = (g, d) of
+// pair_D depths <-> target row d * pair_nv + g (the depth-major order the residual rows and the quantiser launches use).
+struct SoftCeArgs {
+    const float* logits;    // [rows][ld]
+    long ld;
+    const float* targets;   // [rows][ldt]
+    long ldt;
+    int rows, V;
+    int pair_D;
+    long pair_nv;
+    float* out;             // [rows]
+};
+int rq_launch_soft_ce(const SoftCeArgs& a, hipStream_t s);
+
+// residual rows of given codes: out[d * n_vec + g][:] = z[vec0 + g][:] - e_0(c_0) - ... - e_{d-1}(c_{d-1}), c = codes[vec0 + g][:], subtracted
+// one depth after the other in fp32 as the quantiser does (csrc/quantize.hip: rq_split_combine_kernel), so the rows carry its bits
+struct ResidRowsArgs {
+    const float* z;         // [.][dim]
+    const int64_t* codes;   // [.][D]
+    const float* cb[8];
+    int K[8];
+    long vec0, n_vec;
+    int D, dim;             // dim % 4 == 0
+    float* out;             // [D][n_vec][dim]
+};
+int rq_launch_resid_rows(const ResidRowsArgs& a, hipStream_t s);
+
 int rq_launch_set_int(int* p, int v, hipStream_t s);
 int rq_launch_add_int(int* p, int v, hipStream_t s);

@@ -2515,6 +2515,127 @@ int rq_launch_log_prob(const LogProbArgs& a, hipStream_t s) {
     return rq_check_launch("log_prob_kernel");
 }
 
+// Soft-target cross entropy (rqvae/optimizer/loss.py:68-76), one workgroup per row like log_prob_kernel: one pass over the logits row x
+// and the target row t, each thread keeping a running (max, sum of exp) of x plus sum t and sum t x; then
+//   loss = -(sum t x) + (sum t) (m + log(S + 1e-7))
+// which is sum -t (x - m - log(S + 1e-7)) for any weights t (they need not sum to 1; an all-zero row gives 0).  Zero targets are
+// not skipped: 0 * -inf is NaN here as it is there, a NaN logit makes the row NaN, -inf under a positive target gives +inf.
+template <bool VEC>
+__global__ __launch_bounds__(SMP_T) void soft_ce_kernel(SoftCeArgs p) {
+    __shared__ float red[8];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = p.logits + (long)row * p.ld;
+    const float* tg = p.targets + (long)row * p.ldt;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    float m = NEG_INF, sum = 0.f, st = 0.f, stx = 0.f;
+    auto take = [&](float v, float t) {
+        if (v > m) { sum = sum * expf(m - v) + 1.0f; m = v; }
+        else if (!(v <= NEG_INF)) sum += expf(v - m);
+        st += t;
+        stx = fmaf(t, v, stx);
+    };
+    if (VEC) {
+        for (int i = tid * 4; i < p.V; i += SMP_T * 4) {
+            const f32x4 v = *(const f32x4*)(lg + i), t = *(const f32x4*)(tg + i);
+            take(v[0], t[0]); take(v[1], t[1]); take(v[2], t[2]); take(v[3], t[3]);
+        }
+    } else {
+        for (int i = tid; i < p.V; i += SMP_T) take(lg[i], tg[i]);
+    }
+    const float M = blk_max(m, red);
+    const float S = blk_sum(m > NEG_INF ? sum * expf(m - M) : 0.f, red);
+    const float St = blk_sum(st, red);
+    const float Stx = blk_sum(stx, red);
+    if (tid == 0) p.out[row] = -Stx + St * (M + logf(S + 1e-7f));
+}
+
+// The same with the targets given as logits a (t = softmax(a), never written): a running (max, sum of exp) of both rows and
+// W = sum exp(a - m_a) x, rescaled on each new maximum of a like the sums;  loss = -(W / S_a) + (m_x + log(S_x + 1e-7)).
+template <bool VEC>
+__global__ __launch_bounds__(SMP_T) void soft_ce_pair_kernel(SoftCeArgs p) {
+    __shared__ float red[8];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lg = p.logits + (long)row * p.ld;
+    const float* tl = p.targets + ((long)(row % p.pair_D) * p.pair_nv + row / p.pair_D) * p.ldt;
+    const float NEG_INF = -__int_as_float(0x7f800000);
+    float m = NEG_INF, sum = 0.f, ma = NEG_INF, sa = 0.f, w = 0.f;
+    auto take = [&](float v, float a) {
+        if (v > m) { sum = sum * expf(m - v) + 1.0f; m = v; }
+        else if (!(v <= NEG_INF)) sum += expf(v - m);
+        if (a > ma) { const float r = expf(ma - a); sa = sa * r + 1.0f; w = fmaf(w, r, v); ma = a; }
+        else { const float e = expf(a - ma); sa += e; w = fmaf(e, v, w); }
+    };
+    if (VEC) {
+        for (int i = tid * 4; i < p.V; i += SMP_T * 4) {
+            const f32x4 v = *(const f32x4*)(lg + i), a = *(const f32x4*)(tl + i);
+            take(v[0], a[0]); take(v[1], a[1]); take(v[2], a[2]); take(v[3], a[3]);
+        }
+    } else {
+        for (int i = tid; i < p.V; i += SMP_T) take(lg[i], tl[i]);
+    }
+    const float M = blk_max(m, red);
+    const float S = blk_sum(m > NEG_INF ? sum * expf(m - M) : 0.f, red);
+    const float MA = blk_max(ma, red);
+    const float sc = ma > NEG_INF ? expf(ma - MA) : 0.f;          // (a thread without an element: nothing to add)
+    const float SA = blk_sum(sa * sc, red);
+    const float W = blk_sum(w * sc, red);
+    if (tid == 0) p.out[row] = -(W / SA) + (M + logf(S + 1e-7f));
+}
+
+int rq_launch_soft_ce(const SoftCeArgs& a, hipStream_t s) {
+    if (a.rows < 1) return RQAMD_OK;
+    if (a.V < 1 || a.ld < a.V || a.ldt < a.V) return rq_fail(RQAMD_ERR_INVALID, "soft_ce: vocab = %d, leading dimensions %ld / %ld", a.V, a.ld, a.ldt);
+    if (a.pair_D && (a.pair_D < 1 || a.pair_nv < 1 || a.rows != a.pair_D * a.pair_nv))
+        return rq_fail(RQAMD_ERR_INVALID, "soft_ce: %d rows are not %d depths of %ld vectors", a.rows, a.pair_D, a.pair_nv);
+    // 16-byte loads when every row of both matrices starts on 16 bytes and holds whole groups of four
+    const bool vec = (a.V & 3) == 0 && (a.ld & 3) == 0 && (a.ldt & 3) == 0 && (((uintptr_t)a.logits | (uintptr_t)a.targets) & 15) == 0;
+    const dim3 g((unsigned)a.rows), b(SMP_T);
+    if (a.pair_D) {
+        if (vec) RQ_LAUNCH(soft_ce_pair_kernel<true>, g, b, 0, s, a);
+        else RQ_LAUNCH(soft_ce_pair_kernel<false>, g, b, 0, s, a);
+        return rq_check_launch("soft_ce_pair_kernel");
+    }
+    if (vec) RQ_LAUNCH(soft_ce_kernel<true>, g, b, 0, s, a);
+    else RQ_LAUNCH(soft_ce_kernel<false>, g, b, 0, s, a);
+    return rq_check_launch("soft_ce_kernel");
+}
+
+// rqamd_soft_ce (include/rqamd.h): the plain form on its own
+extern "C" int rqamd_soft_ce(const float* logits, int64_t ld_logits, const float* targets, int64_t ld_targets, int64_t rows, int vocab,
+                             float* loss_out, void* stream) {
+    if (rows == 0) return RQAMD_OK;
+    if (!logits || !targets || !loss_out) return rq_fail(RQAMD_ERR_INVALID, "soft_ce: null argument");
+    if (rows < 0 || rows > 0x7fffffffL) return rq_fail(RQAMD_ERR_INVALID, "soft_ce: %ld rows (0 .. 2^31 - 1)", (long)rows);
+    SoftCeArgs a{};
+    a.logits = logits; a.ld = ld_logits; a.targets = targets; a.ldt = ld_targets; a.rows = (int)rows; a.V = vocab; a.out = loss_out;
+    return rq_launch_soft_ce(a, (hipStream_t)stream);
+}
+
+// ResidRowsArgs (rqt_kernels.h): one thread per (vector, four dims), the depths one after the other
+__global__ __launch_bounds__(256) void resid_rows_kernel(ResidRowsArgs p) {
+    const int f4 = p.dim / 4;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= p.n_vec * f4) return;
+    const long g = gid / f4;
+    const int f = (int)(gid - g * f4);
+    f32x4 rv = *(const f32x4*)(p.z + (p.vec0 + g) * p.dim + f * 4);
+    for (int d = 0; d < p.D; ++d) {
+        *(f32x4*)(p.out + ((long)d * p.n_vec + g) * p.dim + f * 4) = rv;
+        if (d + 1 == p.D) break;
+        const long code = p.codes[(p.vec0 + g) * p.D + d];
+        if (code < 0 || code >= p.K[d]) rq_trap();       // an index error in the reference (F.embedding); never a read outside the codebook
+        const f32x4 qv = *(const f32x4*)(p.cb[d] + code * p.dim + f * 4);
+        rv = rv - qv;
+    }
+}
+int rq_launch_resid_rows(const ResidRowsArgs& a, hipStream_t s) {
+    if (a.n_vec < 1) return RQAMD_OK;
+    if (a.D < 1 || a.D > 8 || a.dim < 4 || a.dim % 4) return rq_fail(RQAMD_ERR_INVALID, "resid_rows: depth %d, dim %d", a.D, a.dim);
+    const long work = a.n_vec * (a.dim / 4);
+    RQ_LAUNCH(resid_rows_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, a);
+    return rq_check_launch("resid_rows_kernel");
+}
+
 // -------------------------------------------------------------------------------------------------
 // diagnostics (include/rqamd.h): the attention launchers alone, for the stand-alone fp64 checks (tests/rqt_attn_cases.py).  Each entry
 // fills the launcher's argument struct and calls it unchanged; what the kernels would trap on is refused here, before any launch.

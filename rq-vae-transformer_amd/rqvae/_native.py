@@ -63,6 +63,7 @@ _SIGS = {
                                  C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_sample_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_soft_ce': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_sample_logits_rows': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_sample_logits_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p,
@@ -98,6 +99,8 @@ _SIGS = {
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward_onepass': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_log_probs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_soft_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_set_code': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -303,6 +306,33 @@ def rq_soft_codes(x, codebooks, norms, temp=1.0, stochastic=False, seed=0, offse
                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), ptr(soft), ptr(codes), ptr(ws), ws.numel(),
                                         stream_of(x)))
     return soft, codes
+
+
+def soft_ce(logits, targets, out=None):
+    """soft_target_cross_entropy(logits, targets, reduction='none') (rqvae/optimizer/loss.py:68-84): logits, targets (rows, V) fp32 whose
+    rows are contiguous (any row stride >= V: a column slice of a wider matrix is taken as it is) -> (rows,) fp32.  out: buffer to write into."""
+    if logits.dim() != 2 or tuple(targets.shape) != tuple(logits.shape):
+        raise ValueError(f'soft_ce: logits {tuple(logits.shape)} and targets {tuple(targets.shape)} must be two (rows, V) matrices of one shape')
+    rows, V = logits.shape
+
+    def rows_of(t):
+        if t.dtype != torch.float32:
+            raise ValueError(f'expected torch.float32, got {t.dtype}')
+        if rows and V and (t.stride(1) != 1 or (rows > 1 and t.stride(0) < V)):
+            t = t.contiguous()
+        # (ptr() validates a contiguous tensor: pass the address of the first row and the row stride)
+        return t, (t.stride(0) if rows > 1 else V)
+    logits, ld = rows_of(logits)
+    targets, ldt = rows_of(targets)
+    out = _out_like(out, (rows,), torch.float32, logits.device, 'soft_ce')
+    if rows == 0:
+        return out
+    if V < 1:
+        raise ValueError('soft_ce: empty rows')
+    with on_device_of(logits):
+        check(lib().rqamd_soft_ce(ptr(logits.as_strided((1,), (1,)), torch.float32), ld, ptr(targets.as_strided((1,), (1,)), torch.float32), ldt,
+                                  rows, V, ptr(out), stream_of(logits)))
+    return out
 
 
 def rq_distances(x, codebook, norms, out=None):
@@ -918,6 +948,46 @@ class RqtEngine(_Engine):
         cbs = _ptr_array(codebooks[:c.D])
         self._run(lambda: self._L.rqamd_rqt_log_probs(self._h, ptr(codes, torch.int64), ptr(cond, torch.int64), B, cbs,
                                                     ptr(out), ptr(cl), stream_of(codes)))
+        return out if cl is None else (out, cl)
+
+    def soft_loss(self, codes, cond, codebooks, soft_targets=None, z=None, norms=None, temp=1.0):
+        """rqamd_rqt_soft_loss: the soft-target cross entropy of every code (B,H,W,D) fp32 against `soft_targets` (B,H,W,D,V) fp32, or
+        against the soft codes of the features `z` (B,H,W,input_embed_dim) fp32 at temperature `temp` (norms: rq_code_norms of every
+        codebook), formed inside the engine; (that, cond_logp) for text-conditioned models, as log_probs.  Neither the logits nor (from z)
+        the targets are materialised."""
+        self._check(codes, cond, codebooks)
+        B = codes.shape[0]
+        c = self.cfg
+        if (soft_targets is None) == (z is None):
+            raise ValueError('soft_loss: exactly one of soft_targets and z must be given')
+        nrm = None
+        if soft_targets is not None:
+            if tuple(soft_targets.shape) != (B, c.H, c.W, c.D, c.vocab_size):
+                raise ValueError(f'soft_targets of shape {tuple(soft_targets.shape)}; expected {(B, c.H, c.W, c.D, c.vocab_size)}')
+            self._on_my_device(soft_targets)
+        else:
+            if tuple(z.shape) != (B, c.H, c.W, c.input_embed_dim):
+                raise ValueError(f'z of shape {tuple(z.shape)}; expected {(B, c.H, c.W, c.input_embed_dim)}')
+            if norms is None or len(norms) < c.D:
+                raise ValueError(f'soft_loss: z needs the code norms of the {c.D} codebooks')
+            for d in range(c.D):
+                if tuple(codebooks[d].shape) != (c.vocab_size, c.input_embed_dim) or tuple(norms[d].shape) != (c.vocab_size,):
+                    raise NotImplementedError(f'soft_loss: codebook {d} of shape {tuple(codebooks[d].shape)}; the targets need codebooks of '
+                                              f'exactly vocab_size = {c.vocab_size} codes of dim {c.input_embed_dim} with their norms')
+            if not (float(temp) > 0):
+                raise ValueError(f'soft_loss: temp = {temp} must be > 0')
+            self._on_my_device(z, *norms[:c.D])
+            nrm = _ptr_array(norms[:c.D])
+        out = torch.empty((B, c.H, c.W, c.D), dtype=torch.float32, device=codes.device)
+        cl = None
+        if c.block_size_cond > 1:
+            if cond is None:
+                raise ValueError('soft_loss of a text-conditioned model needs cond')
+            cl = torch.empty((B, c.block_size_cond - 1), dtype=torch.float32, device=codes.device)
+        cbs = _ptr_array(codebooks[:c.D])
+        self._run(lambda: self._L.rqamd_rqt_soft_loss(self._h, ptr(codes, torch.int64), ptr(cond, torch.int64), B, cbs,
+                                                    ptr(soft_targets, torch.float32), ptr(z, torch.float32), nrm, float(temp), ptr(out), ptr(cl),
+                                                    stream_of(codes)))
         return out if cl is None else (out, cl)
 
     def set_option(self, name, value):

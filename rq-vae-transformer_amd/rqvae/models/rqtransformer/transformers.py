@@ -305,6 +305,48 @@ class RQTransformer(Stage2Model):
         return self._on_side_stream(xs.device, lambda: eng.log_probs(codes, c, cbs))
 
     @torch.no_grad()
+    def soft_target_loss(self, xs, model_aux=None, cond=None, amp=False, *, soft_targets=None, z_e=None, temp=1.0):
+        """The soft-target cross entropy of every code of `xs` under forward(): (B,H,W,D) fp32 =
+        soft_target_cross_entropy(forward(xs), soft, reduction='none') (rqvae/optimizer/loss.py:68-84), or (that, cond_logp) when
+        block_size_cond > 1, mirroring log_probs.  .mean() is compute_loss(forward(xs), soft, use_soft_target=True) and .mean((0, 1, 2))
+        compute_codebook_loss(...) (transformers.py:371-410) -- the way the reference trains and validates stage 2 -- at any batch
+        size: the loss is reduced from sub-chunks of logits rows inside the engine, (B,H,W,D,V) logits are never allocated.
+        Exactly one of (keyword-only)
+          soft_targets (B,H,W,D,V): the soft codes of model_aux.get_soft_codes(...) that came with `xs`, or any weights;
+          z_e (B,h,w,embed_dim): the encoder features `xs` was quantised from, with `temp` -- the soft codes of get_soft_codes(temp=temp)
+            are formed inside the engine from the residual of the GIVEN codes (argmin or stochastic draws) and never stored.
+        All depths must share one vocabulary (NotImplementedError otherwise, as get_soft_codes refuses ragged codebooks)."""
+        (B, H, W, D) = xs.shape
+        assert torch.Size([H, W, D]) == self.block_size
+        self._cf = None
+        if (soft_targets is None) == (z_e is None):
+            raise ValueError('soft_target_loss: exactly one of soft_targets and z_e must be given')
+        eng = self._eng(amp)
+        codes = xs.to(torch.long).contiguous()
+        c = self._cond(cond, B, xs.device)
+        if c is None and self.block_size_cond > 1:
+            raise ValueError('soft_target_loss of a text-conditioned model needs cond (its tokens are the targets of cond_logp)')
+        V = max(self.vocab_size)
+        if soft_targets is not None:
+            if tuple(soft_targets.shape) != (B, H, W, D, V):
+                raise ValueError(f'soft_targets of shape {tuple(soft_targets.shape)}; expected {(B, H, W, D, V)}')
+            cbs = self._checked_codebooks(model_aux)
+            soft = soft_targets.detach().to(device=xs.device, dtype=torch.float32).contiguous()
+            return self._on_side_stream(xs.device, lambda: eng.soft_loss(codes, c, cbs, soft_targets=soft))
+        if not (float(temp) > 0):
+            raise ValueError(f'soft_target_loss: temp = {temp} must be > 0')
+        quantizer = self._quantizer(model_aux)
+        cbs, norms = quantizer.codebook_list()[:D], quantizer._norm_list()[:D]
+        z = quantizer.to_code_shape(z_e.detach()).to(device=xs.device, dtype=torch.float32).contiguous()
+        return self._on_side_stream(xs.device, lambda: eng.soft_loss(codes, c, cbs, z=z, norms=norms, temp=float(temp)))
+
+    @staticmethod
+    def _quantizer(model_aux):
+        if model_aux is None or not hasattr(model_aux, 'quantizer'):
+            raise ValueError('soft_target_loss(z_e=...) needs model_aux, the RQVAE whose quantiser produced the codes')
+        return model_aux.quantizer
+
+    @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, keep_mask=None):
         """transformers.py:294-369.  ``keep_mask`` (not in the reference; keyword-only): codes of `partial_sample` to hold fixed --
@@ -744,10 +786,24 @@ class RQTransformer(Stage2Model):
             offset = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) * 4     # CPU generator (emulator tests)
         return seed, offset
 
+    @staticmethod
+    def _soft_ce_rows(logits, targets):
+        """soft_target_cross_entropy(logits, targets, reduction='none') (rqvae/optimizer/loss.py:68-84) over the flattened rows, on the
+        GPU (rqamd_soft_ce): any leading shape, fp32 or fp64 logits (the kernel computes in fp32), views made contiguous."""
+        if logits.requires_grad:
+            raise NotImplementedError('soft-target cross entropy of logits that require grad: this package has no backward pass '
+                                      '(detach the logits to evaluate the loss)')
+        if logits.shape != targets.shape:
+            raise ValueError(f'soft targets of shape {tuple(targets.shape)} for logits of shape {tuple(logits.shape)}')
+        V = logits.shape[-1]
+        x = logits.detach().reshape(-1, V).to(torch.float32).contiguous()
+        t = targets.detach().reshape(-1, V).to(device=x.device, dtype=torch.float32).contiguous()
+        return _native.soft_ce(x, t)
+
     def compute_loss(self, logits, targets, use_soft_target=False):
-        """transformers.py:371-382 (hard targets; soft targets are training-side)."""
+        """transformers.py:371-382; use_soft_target: soft_target_cross_entropy (rqvae/optimizer/loss.py:68-84) on the GPU, no backward."""
         if use_soft_target:
-            raise NotImplementedError('soft-target cross entropy (RQ-Transformer training) is out of scope')
+            return self._soft_ce_rows(logits, targets).mean()
         return F.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
 
     def compute_cond_loss(self, cond_logits, conds):
@@ -757,9 +813,9 @@ class RQTransformer(Stage2Model):
 
     @torch.no_grad()
     def compute_codebook_loss(self, logits, targets, use_soft_target=False):
-        """transformers.py:393-410: the cross entropy of each depth (codebook) separately, (D,) -- hard targets only."""
-        if use_soft_target:
-            raise NotImplementedError('soft-target cross entropy (RQ-Transformer training) is out of scope')
+        """transformers.py:393-410: the cross entropy of each depth (codebook) separately, (D,); use_soft_target as in compute_loss."""
         D = logits.shape[-2]
+        if use_soft_target:
+            return self._soft_ce_rows(logits, targets).reshape(-1, D).mean(dim=0)
         per_code = F.cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1), reduction='none')
         return per_code.reshape(-1, D).mean(dim=0)
