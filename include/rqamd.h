@@ -207,7 +207,17 @@ int rqamd_rqt_destroy(rqamd_rqt* h);
 /* options of a handle that the config struct does not carry (ABI v7).  "head.n_head" <- head.block.n_head where it differs from
  * body.block.n_head = cfg.n_head (transformers.py:86-87: each AttentionStack has its own block config; attentions.py:44-57: any
  * embed_dim / n_head).  Head size 64 -- every released config -- takes the tuned attention kernels; any other size <= 256 a plain
- * wavefront-per-(row, head) kernel (bf16 / fp16 cache only: the RQAMD_KV 8-bit formats need 64). */
+ * wavefront-per-(row, head) kernel (bf16 / fp16 cache only: the RQAMD_KV 8-bit formats need 64).
+ * "prefix.one_pass" (0 | 1, default 0; additive, ABI v7): how rqamd_rqt_sample, _sample_masked, _sample_guided and _sample_rows (armed by
+ * rqamd_rqt_sample_logp or not) bring the given leading positions into the body stack's KV cache.  n0 = the number of leading
+ * positions before start_h / start_w or with pos_active_host 0.  0: one body-only step per position (B rows each, the whole body
+ * weight set streamed n0 times).  1, with n0 >= 1 and some position to draw: tokens 0 .. block_size_cond - 1 + n0 - 2 of every row
+ * -- the conditioning tokens, then the embeddings of positions 0 .. n0 - 2 -- go through the body stack in ONE pass (rows chunked by
+ * "fwd.chunk_rows", in the one-pass forward's workspace; a guided call prefills both twins, each under its own conditioning), the
+ * position counter is set to n0 and the usual loop goes on from there.  For a text-conditioned model the pass replaces the
+ * text-only prefill.  Later positions see the same arithmetic through other GEMM tiles: logits differ by rounding, so a draw that was
+ * close may come out differently -- filters and Philox counters are the same.  Captured graphs are shared by the two settings; model
+ * log-probabilities stay NaN and draw +0.0 at the prefix positions.  Kept runs that are not leading stay stepped. */
 int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value);
 int rqamd_rqt_set_param(rqamd_rqt* h, const char* name, const float* dev_ptr, const int64_t* shape,
                         int ndim, void* stream);
@@ -341,11 +351,16 @@ int rqamd_rqt_soft_loss(rqamd_rqt* h, const int64_t* codes, const int64_t* cond,
  *                  (pos ascending, d = 0..D-1); d < 0 runs only the body stack of that position (positions before start_loc,
  *                  whose codes are given: KV cache only).  *logits_dev points into the handle's workspace and is valid until
  *                  the next call on the handle.  Columns >= vocab_sizes[d] are masked to -inf (LogitMask).
+ *   step_prefill   (additive, ABI v7) valid only directly after step_begin, else RQAMD_ERR_STATE: fills the KV cache for positions
+ *                  0 .. n_pos-1 in one pass over the codes of `partial` (see "prefix.one_pass"; the option is not consulted).  Stands
+ *                  for step_logits(p, -1), p < n_pos: the next step_logits must be (n_pos, 0) or (n_pos, -1).  n_pos outside
+ *                  1 .. H*W-1: RQAMD_ERR_INVALID
  *   step_set_code  writes codes[batch] as code (pos, d) of every image
  *   step_end       copies the codes (batch,H,W,D) out (codes_out may be NULL) and ends the sequence.
  * Any other call on the handle ends a sequence in progress. */
 int rqamd_rqt_step_begin(rqamd_rqt* h, const int64_t* partial, const int64_t* cond, int batch,
                          const float* const* codebooks, void* stream);
+int rqamd_rqt_step_prefill(rqamd_rqt* h, int n_pos, void* stream);
 int rqamd_rqt_step_logits(rqamd_rqt* h, int pos, int d, const float** logits_dev, void* stream);
 int rqamd_rqt_step_set_code(rqamd_rqt* h, int pos, int d, const int64_t* codes, void* stream);
 int rqamd_rqt_step_end(rqamd_rqt* h, int64_t* codes_out, void* stream);

@@ -137,6 +137,9 @@ struct rqamd_rqt {
     int fwd_chunk_rows = 4096;    // "fwd.chunk_rows": body rows per chunk of images, head rows per sub-chunk
     int fwd_logits_bytes = 48 << 20;   // "fwd.logits_bytes": the logits sub-chunk the log_probs / soft_loss forms reduce (whole depth groups, at least one)
     DevBuf fws;
+    // "prefix.one_pass": the given leading positions of a sampling call fill the KV cache in one pass (prefix_prefill) instead of one
+    // body-only step each.  Off by default; the captured graphs are the same either way, so the option invalidates nothing
+    bool prefix_one_pass = false;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -287,6 +290,11 @@ extern "C" int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value) {
     if (strcmp(name, "fwd.logits_bytes") == 0) { // size of the logits sub-chunk of rqamd_rqt_log_probs / rqamd_rqt_soft_loss (tests force the classifier loop to split)
         if (value < 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: fwd.logits_bytes = %d < 1", value);
         h->fwd_logits_bytes = value;
+        return RQAMD_OK;
+    }
+    if (strcmp(name, "prefix.one_pass") == 0) {  // how the sampling entry points fill the KV cache for the given leading positions (include/rqamd.h)
+        if (value != 0 && value != 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: prefix.one_pass = %d (0 or 1)", value);
+        h->prefix_one_pass = value == 1;
         return RQAMD_OK;
     }
     return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: unknown option '%s'", name);
@@ -727,7 +735,9 @@ static int position_sequence(rqamd_rqt* h, const StepCtx& c, bool first_pos, boo
 // inputs into the workspace, position counter to 0, conditioning prefix through the body stack
 // (guided sampling: `partial` and `cond` / `uncond` hold c.Bs rows each -- the codes go into both halves of h->xs, the two conditionings
 // into the two halves of h->cond)
-static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const int64_t* cond, hipStream_t st, const int64_t* uncond = nullptr) {
+// skip_text: the caller runs the conditioning prefix itself, merged with the given code positions (prefix_prefill)
+static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, const int64_t* cond, hipStream_t st, const int64_t* uncond = nullptr,
+                       bool skip_text = false) {
     const int B = c.B;
     h->step_on = false;                            // any new batch ends a stepping sequence (same workspace)
     RQ_TRY(ensure_batch(h, B));
@@ -747,7 +757,7 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
     // forward() their body outputs also feed cond_classifier, :150-153).  All P = cond_len-1 tokens of a chunk of images go
     // through the body stack in ONE pass (GEMMs over images x P rows, causal attention inside the prefix), the way the
     // reference's first cached step does -- not as P sequential single-token steps.
-    if (h->cond_len > 1) {
+    if (h->cond_len > 1 && !skip_text) {
         const int P = h->cond_len - 1, pc = prefill_chunk(h, B), vc = h->cfg.vocab_size_cond < 1 ? 1 : h->cfg.vocab_size_cond;
         for (int b0 = 0; b0 < B; b0 += pc) {
             PrefillCtx pf{b0, B - b0 < pc ? B - b0 : pc, P};
@@ -770,6 +780,8 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
     return RQAMD_OK;
 }
 
+static int prefix_prefill(rqamd_rqt* h, const float* const* codebooks, int B, int n0, hipStream_t st);
+
 // `keep` / `pos_active` (masked sampling): device flags per code, copied into h->keep before anything reads them, and the host's
 // per-position activity (null: every position).  An inactive position has every code given in every row: body stack only, like the
 // positions before start_idx.  Nothing runs after the last active position -- nobody reads its KV entries.
@@ -778,15 +790,21 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
                    const int64_t* uncond = nullptr, rqamd_rqt::LogpArm arm = {}) {
     StepCtx c = c_in;
     const int n_in = c.guided ? c.Bs : c.B;              // rows of the caller's arrays (guided: the engine runs c.B = 2 * n_in rows)
-    RQ_TRY(begin_batch(h, c, partial, cond, st, uncond));
     int n_pos = h->HW;
+    while (keep && pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
+    // "prefix.one_pass": n0 = the leading positions whose codes are given in every row (before start_idx, or promised away by pos_active).
+    // Their tokens -- and the text tokens before them -- go through the body stack in one pass, and the loop below starts at n0
+    int n0 = 0;
+    if (h->prefix_one_pass && c.sample)
+        while (n0 < n_pos && (n0 < start_idx || (pos_active && !pos_active[n0]))) ++n0;
+    RQ_TRY(begin_batch(h, c, partial, cond, st, uncond, n0 >= 1));
     if (keep) {
         const size_t kb = (size_t)n_in * h->HW * h->D;
         RQ_HIP(hipMemcpyAsync(h->keep, keep, kb, hipMemcpyDeviceToDevice, st));
         if (c.guided) RQ_HIP(hipMemcpyAsync(h->keep + kb, keep, kb, hipMemcpyDeviceToDevice, st));   // (the sampler reads rows 0..Bs-1)
         c.keep = h->keep;
-        while (pos_active && n_pos > 0 && !pos_active[n_pos - 1]) --n_pos;
     }
+    if (n0 >= 1 && n0 < n_pos) RQ_TRY(prefix_prefill(h, c.codebooks, c.B, n0, st));      // (n0 == n_pos: no position draws, nothing runs)
     if (c.logp) {          // outside any capture: what no step writes stays +0.0 (draw: kept codes, codes before start_idx) / NaN (model: no head ran)
         const long n = (long)c.B * h->HW * h->D;
         RQ_HIP(hipMemsetAsync(h->logp_draw, 0, (size_t)n * 4, st));
@@ -795,7 +813,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
     }
     const int fam = (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
-    for (int pos = 0; pos < n_pos; ++pos) {
+    for (int pos = n0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
         const bool graphable = use_graph && c.sample && do_head && pos >= 1 && !h->prof.on;
         if (graphable) {
@@ -1085,6 +1103,64 @@ struct WorkspaceSwap {
     ~WorkspaceSwap() { h->x = x; h->xh = xh; h->slabs = slabs; h->y = y; h->qkv = qkv; h->ya = ya; h->hbuf = hbuf; h->ain = ain; }
 };
 
+// One-pass prefix prefill ("prefix.one_pass", rqamd_rqt_step_prefill): the codes of spatial positions 0 .. n0-1 of the B rows in h->xs are
+// given, so their body tokens need not be stepped.  Tokens 0 .. Pn-1 of every image, Pn = cond_len - 1 + n0 -- all cond_len conditioning
+// tokens, then the embeddings of positions 0 .. n0-2 -- run through the body stack in ONE pass the way the reference's first cached step
+// does (transformers.py:235-239), and K / V are appended to the layers' caches at 0 .. Pn-1; the device position counter is left at
+// n0, where the position loop goes on with the embedding of position n0-1 as its input.  For a text-conditioned model this IS the
+// prefill of the text prefix (begin_batch skips its own): one sequence per image, text tokens then code tokens.
+// Rows live in h->fws (WorkspaceSwap), chunked over images so that n_img * Pn <= fwd_chunk_rows (one image at least): h->ws / h->kv stay
+// where the captured graphs expect them.  Inputs as forward_onepass forms them (gather_codes / body_input with n0 positions per
+// image), attention through the appending form of rq_launch_attn_prefill, whichever kernel it picks for Pn tokens: plain up to 255, tiled
+// beyond, the one-wavefront-per-token kernel for head sizes other than 64, quantising for the 8-bit caches (Tbody <= 256 there, so Pn <= 255).
+static int prefix_prefill(rqamd_rqt* h, const float* const* codebooks, int B, int n0, hipStream_t st) {
+    const int E = h->E, D = h->D, HW = h->HW, Pn = h->cond_len - 1 + n0;
+    const int vc = h->cfg.vocab_size_cond < 1 ? 1 : h->cfg.vocab_size_cond;
+    if (n0 < 1 || n0 >= HW || B < 1 || B > h->cap) return rq_fail(RQAMD_ERR_INVALID, "rqt prefix prefill: %d positions, %d rows (capacity %d)", n0, B, h->cap);
+    int n_img = h->fwd_chunk_rows / Pn;            // images per chunk
+    if (n_img < 1) n_img = 1;
+    if (n_img > B) n_img = B;
+    const size_t rows = (size_t)n_img * Pn;        // (h->xh holds the n_img * (n0 - 1) input_mlp rows: fewer)
+    const size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
+                         + al(rows * 4 * E * 2) + al(rows * h->Din * 2);
+    RQ_TRY(h->fws.reserve(total));
+    WorkspaceSwap keep(h);
+    char* p = (char*)h->fws.p;
+    auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
+    h->x = (float*)take(rows * E * 4); h->xh = (float*)take(rows * E * 4);
+    h->slabs = (float*)take((size_t)h->max_slabs * rows * E * 4);
+    h->y = (bf16_t*)take(rows * E * 2); h->ya = (bf16_t*)take(rows * E * 2);
+    h->qkv = (bf16_t*)take(rows * 3 * E * 2); h->hbuf = (bf16_t*)take(rows * 4 * E * 2);
+    h->ain = (bf16_t*)take(rows * h->Din * 2);
+    for (int b0 = 0; b0 < B; b0 += n_img) {
+        const int n = B - b0 < n_img ? B - b0 : n_img;
+        const int64_t* ccodes = h->xs + (long)b0 * HW * D;
+        BodyInputArgs bi{};
+        bi.cond = h->cond + (long)b0 * h->cond_len; bi.cond_stride = h->cond_len; bi.cond_len = h->cond_len; bi.vocab_cond = vc;
+        bi.cond_emb = h->cond_emb; bi.pos_cond = h->pos_cond; bi.bias_tab = h->body_in_bias; bi.pos_tab = h->pos_hw;
+        bi.n_img = n; bi.HW = HW; bi.n_pos = n0; bi.D = D; bi.E = E; bi.x = h->x;
+        if (h->in_vq) {
+            if (n0 > 1) {
+                GatherCodesArgs g{};
+                g.codes = ccodes; g.head = 0; g.cumsum = 1; g.row0 = 0; g.rows = n * (n0 - 1); g.HW = HW; g.n_pos = n0; g.D = D; g.dim = h->Din; g.out = h->ain;
+                for (int d = 0; d < D; ++d) { g.cb[d] = codebooks[d]; g.K[d] = h->Vd[d]; }
+                RQ_TRY(rq_launch_gather_codes(g, st));
+                RQ_TRY(step_gemm(h, h->ain, h->Din, h->w_in, g.rows, E, h->Din, EPI_F32, nullptr, nullptr, 0, h->xh, E, nullptr, st));
+            }
+            bi.emb = h->xh;
+        } else {
+            bi.codes = ccodes; bi.table = h->tok_emb;
+            for (int d = 0; d < D; ++d) { bi.offs[d] = h->tok_offs[d]; bi.V[d] = h->Vd[d]; }
+        }
+        RQ_TRY(rq_launch_body_input(bi, st));
+        Pending pend{nullptr, 0, nullptr};         // (the last layer's fc2 output feeds nothing: no head runs for a prefix position)
+        const PrefillCtx pf{b0, n, Pn};
+        h->cur_gelu_v2 = h->cfg.gelu_v2 == 1 || h->cfg.gelu_v2 == 3;
+        for (auto& L : h->body) RQ_TRY(run_block(h, L, h->x, h->x, pend, nullptr, n * Pn, nullptr, 0, 0, h->Tbody, st, &pf));
+    }
+    return rq_launch_set_int(h->st, n0, st);
+}
+
 static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int B, const float* const* codebooks,
                            const OnePassOut& o, hipStream_t st) {
     h->step_on = false;                            // ends a stepping sequence like any other call
@@ -1143,11 +1219,11 @@ static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* co
         // ---- body input: conditioning tokens + the embeddings of spatial positions 0 .. HW-2 (transformers.py:127-137)
         BodyInputArgs bi{};
         bi.cond = ccond; bi.cond_stride = h->cond_len; bi.cond_len = h->cond_len; bi.vocab_cond = vc; bi.cond_emb = h->cond_emb; bi.pos_cond = h->pos_cond;
-        bi.bias_tab = h->body_in_bias; bi.pos_tab = h->pos_hw; bi.n_img = n; bi.HW = HW; bi.D = D; bi.E = E; bi.x = h->x;
+        bi.bias_tab = h->body_in_bias; bi.pos_tab = h->pos_hw; bi.n_img = n; bi.HW = HW; bi.n_pos = HW; bi.D = D; bi.E = E; bi.x = h->x;
         if (h->in_vq) {
             if (HW > 1) {
                 GatherCodesArgs g{};
-                g.codes = ccodes; g.head = 0; g.cumsum = 1; g.row0 = 0; g.rows = n * (HW - 1); g.HW = HW; g.D = D; g.dim = h->Din; g.out = h->ain;
+                g.codes = ccodes; g.head = 0; g.cumsum = 1; g.row0 = 0; g.rows = n * (HW - 1); g.HW = HW; g.n_pos = HW; g.D = D; g.dim = h->Din; g.out = h->ain;
                 for (int d = 0; d < D; ++d) { g.cb[d] = codebooks[d]; g.K[d] = h->Vd[d]; }
                 RQ_TRY(rq_launch_gather_codes(g, st));
                 RQ_TRY(step_gemm(h, h->ain, h->Din, h->w_in, g.rows, E, h->Din, EPI_F32, nullptr, nullptr, 0, h->xh, E, nullptr, st));
@@ -1357,6 +1433,19 @@ extern "C" int rqamd_rqt_step_begin(rqamd_rqt* h, const int64_t* partial, const 
     c.B = batch; c.codebooks = h->step_cb; c.temperature = 1.f; c.sample = false;
     RQ_TRY(begin_batch(h, c, partial, cond, (hipStream_t)stream));
     h->step_on = true; h->step_B = batch; h->step_pos = 0; h->step_d = 0;
+    return RQAMD_OK;
+}
+
+// the body-only steps (p, -1), p < n_pos, of a sequence that has just begun, in one pass (prefix_prefill; whatever "prefix.one_pass" says).
+// The text prefix that step_begin has cached is run again as the head of the merged sequences: the same rows, rewritten
+extern "C" int rqamd_rqt_step_prefill(rqamd_rqt* h, int n_pos, void* stream) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_step_prefill: null handle");
+    if (!h->step_on || h->step_pos != 0 || h->step_d != 0)
+        return rq_fail(RQAMD_ERR_STATE, "rqt_step_prefill: valid only directly after rqamd_rqt_step_begin");
+    if (n_pos < 1 || n_pos > h->HW - 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_step_prefill: n_pos = %d outside 1 .. %d", n_pos, h->HW - 1);
+    if (h->cap < h->step_B) return rq_fail(RQAMD_ERR_STATE, "rqt_step_prefill: the workspace was re-sized by another call");
+    RQ_TRY(prefix_prefill(h, h->step_cb, h->step_B, n_pos, (hipStream_t)stream));
+    h->step_pos = n_pos; h->step_d = 0;
     return RQAMD_OK;
 }
 

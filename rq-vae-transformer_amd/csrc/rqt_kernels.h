@@ -143,7 +143,9 @@ int rq_launch_cvt_bf16_transpose(const float* src, bf16_t* dst, int R, int Cc, h
 // Body rows are ordered (image, token), head rows (image, position, depth) -- the order of the logits.
 
 // codebook rows summed over depth -> bf16 GEMM operand, for all rows of a chunk (embed_tokens_kernel for one position at a time):
-//   body (head == 0): row R = (image, q), q = 0 .. HW-2: sum over all depths of the codes at spatial position q
+//   body (head == 0): row R = (image, q), q = 0 .. n_pos-2: sum over all depths of the codes at spatial position q.  n_pos = HW: every
+//        position that is ever embedded (the one-pass forward); n_pos = n0 < HW: the given prefix of a sampling call (engine_rqt.hip:
+//        prefix_prefill), whose position n0-1 the first decode step embeds.  HW stays the stride of `codes`
 //   head (head == 1): row R = (g, d), g = image * HW + position: sum over depths [cumsum ? 0 : d-1, d) of the codes at g (d == 0: zeros)
 struct GatherCodesArgs {
     const int64_t* codes;   // [n_img][HW][D] codes of the chunk
@@ -152,24 +154,26 @@ struct GatherCodesArgs {
     int head, cumsum;
     long row0;              // first row of this launch (rows are counted from the start of the chunk)
     int rows, HW, D, dim;
+    int n_pos;              // body form: positions per image, n_pos - 1 rows each (2 .. HW); the head form ignores it
     bf16_t* out;            // [rows][dim]
 };
 int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s);
 
-// body input rows (image, t), t = 0 .. Tb-1: t < cond_len: cond_emb[cond[image][t]] + pos_emb_cond[t]; else, with q = t - cond_len:
+// body input rows (image, t), t = 0 .. Tb-1, Tb = cond_len - 1 + n_pos (n_pos = HW: the whole map; n_pos = n0: a given prefix): t < cond_len: cond_emb[cond[image][t]] + pos_emb_cond[t]; else, with q = t - cond_len:
 // emb[(image, q)] + bias_tab[q] (emb = the input_mlp GEMM over GatherCodesArgs rows), or -- table non-null -- pos_tab[q] + sum_d table[offs[d] + code_d]
 struct BodyInputArgs {
     const int64_t* cond;    // [n_img][cond_stride] or null (class 0)
     int cond_stride, cond_len, vocab_cond;
     const float *cond_emb, *pos_cond;
-    const float* emb;       // [n_img * (HW-1)][E] or null
+    const float* emb;       // [n_img * (n_pos-1)][E] or null
     const float* bias_tab;  // [HW][E] (body_in_bias)
     const int64_t* codes;   // [n_img][HW][D] (learned token embeddings only)
     const float* table;     // [sum V][E] or null
     int offs[8], V[8];
     const float* pos_tab;   // [HW][E] (pos_emb_hw)
     int n_img, HW, D, E;
-    float* x;               // [n_img * Tb][E], Tb = cond_len - 1 + HW
+    int n_pos;              // positions per image, 1 .. HW (HW is the stride of `codes` and the height of the tables)
+    float* x;               // [n_img * Tb][E]
 };
 int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s);
 

@@ -2272,8 +2272,8 @@ __global__ void gather_codes_kernel(GatherCodesArgs p) {
         hi = (int)(R - cpos * p.D);
         lo = p.cumsum ? 0 : (hi > 0 ? hi - 1 : 0);
     } else {
-        const long img = R / (p.HW - 1);
-        cpos = img * p.HW + (R - img * (p.HW - 1));
+        const long img = R / (p.n_pos - 1);
+        cpos = img * p.HW + (R - img * (p.n_pos - 1));
         lo = 0; hi = p.D;
     }
     const int64_t* codes = p.codes + cpos * p.D;
@@ -2296,13 +2296,14 @@ __global__ void gather_codes_kernel(GatherCodesArgs p) {
 int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s) {
     if (a.dim % 8 != 0) return rq_fail(RQAMD_ERR_UNSUPPORTED, "embed: dim %d %% 8 != 0", a.dim);
     if (a.rows < 1) return RQAMD_OK;
+    if (!a.head && (a.n_pos < 2 || a.n_pos > a.HW)) return rq_fail(RQAMD_ERR_INVALID, "gather_codes: %d positions per image (2 .. %d)", a.n_pos, a.HW);
     const long n = (long)a.rows * (a.dim / 8);
     RQ_LAUNCH(gather_codes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return rq_check_launch("gather_codes_kernel");
 }
 
 __global__ void body_input_kernel(BodyInputArgs p) {
-    const int per_row = p.E / 4, Tb = p.cond_len - 1 + p.HW;
+    const int per_row = p.E / 4, Tb = p.cond_len - 1 + p.n_pos;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)p.n_img * Tb * per_row) return;
     const long row = gid / per_row;
@@ -2326,13 +2327,14 @@ __global__ void body_input_kernel(BodyInputArgs p) {
                 v = v + *(const f32x4*)(p.table + ((long)p.offs[d] + code) * p.E + c);
             }
         } else {
-            v = *(const f32x4*)(p.emb + (img * (p.HW - 1) + q) * p.E + c) + *(const f32x4*)(p.bias_tab + (long)q * p.E + c);
+            v = *(const f32x4*)(p.emb + (img * (p.n_pos - 1) + q) * p.E + c) + *(const f32x4*)(p.bias_tab + (long)q * p.E + c);
         }
     }
     *(f32x4*)(p.x + row * p.E + c) = v;
 }
 int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s) {
-    const long n = (long)a.n_img * (a.cond_len - 1 + a.HW) * (a.E / 4);
+    if (a.n_pos < 1 || a.n_pos > a.HW) return rq_fail(RQAMD_ERR_INVALID, "body_input: %d positions per image (1 .. %d)", a.n_pos, a.HW);
+    const long n = (long)a.n_img * (a.cond_len - 1 + a.n_pos) * (a.E / 4);
     RQ_LAUNCH(body_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return rq_check_launch("body_input_kernel");
 }

@@ -102,6 +102,7 @@ _SIGS = {
     'rqamd_rqt_soft_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    'rqamd_rqt_step_prefill': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'rqamd_rqt_step_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_set_code': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_end': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1001,6 +1002,15 @@ class RqtEngine(_Engine):
         cbs = _ptr_array(self._step[2])
         self._run(lambda: self._L.rqamd_rqt_step_begin(self._h, ptr(partial, torch.int64), ptr(cond, torch.int64), partial.shape[0], cbs,
                                                      stream_of(partial)))
+
+    def step_prefill(self, n_pos):
+        """directly after step_begin: the KV cache of positions 0 .. n_pos-1 from the given codes in one pass (rqamd_rqt_step_prefill) --
+        stands for step_logits(p, -1), p < n_pos; the next step is (n_pos, 0)"""
+        step = getattr(self, '_step', None)
+        dev = step[1] if step else self.device
+        with on_device_of(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0)
+            check(self._L.rqamd_rqt_step_prefill(self._h, int(n_pos), st), self._L)
 
     def step_logits(self, pos, d):
         """logits (B, V) fp32 of step (pos, d) -- a view of the engine's workspace, valid until the next engine call; d < 0:

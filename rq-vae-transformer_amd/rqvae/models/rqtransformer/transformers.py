@@ -108,6 +108,13 @@ class RQTransformer(Stage2Model):
         # launch; 'one_pass' (or RQAMD_FORWARD=one_pass): every position at once, no KV cache (rqamd_rqt_forward_onepass) -- same
         # arithmetic, other GEMM tiles.  cached_forward and sample (cached or not) always step.
         self.forward_mode = os.environ.get('RQAMD_FORWARD', 'stepped')
+        # how sample() / sample_guided() / a restarted cached_forward bring the GIVEN leading positions (before start_loc, or a fully
+        # kept leading run of keep_mask) into the body stack's KV cache: 'stepped' (default): one body-only step per position;
+        # 'one_pass' (or RQAMD_PREFIX=one_pass): conditioning tokens and prefix codes through the body stack at once, the way the
+        # reference's first cached step does (engine option "prefix.one_pass" / rqamd_rqt_step_prefill).  Same arithmetic through other
+        # GEMM tiles: the codes drawn after the prefix differ from the stepped mode's wherever a draw was close; filters and Philox
+        # counters are the same.  sample(cached=False) has no cache and is untouched.
+        self.prefix_mode = os.environ.get('RQAMD_PREFIX', 'stepped')
         self._return_log_probs = False                   # inside `with self.return_log_probs()`: sample() also returns SampleLogProbs
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
 
@@ -158,6 +165,21 @@ class RQTransformer(Stage2Model):
             self._engines[amp] = (eng, sig)
         return eng
 
+    def _prefix_one_pass(self):
+        if self.prefix_mode not in ('stepped', 'one_pass'):
+            raise ValueError(f"prefix_mode = {self.prefix_mode!r} ('stepped' or 'one_pass')")
+        return self.prefix_mode == 'one_pass'
+
+    def _sampling_eng(self, amp=False):
+        """_eng(amp) with the engine's "prefix.one_pass" option following self.prefix_mode (touched only when it has to change: a
+        handle of a model that never leaves the default never sees the option)"""
+        want = self._prefix_one_pass()
+        eng = self._eng(amp)
+        if getattr(eng, '_prefix_one_pass', False) != want:
+            eng.set_option('prefix.one_pass', int(want))
+            eng._prefix_one_pass = want
+        return eng
+
     @staticmethod
     def _codebooks(model_aux):
         """model_aux.get_code_emb_with_depth is the only thing the reference uses model_aux for
@@ -203,7 +225,8 @@ class RQTransformer(Stage2Model):
         the engine's stepping entry points (rqamd_rqt_step_begin / _step_logits / _step_set_code: the arithmetic of sample()).  As in
         the reference the calls of a sequence come in sampling order after init_cache(): a call with d == 0 that does not continue
         the previous call starts a sequence -- the codes of the positions before (h, w) are taken from `xs` and only feed the body
-        stack's KV cache (the start_loc > (0, 0) prefill, :235-239; that restart costs `pos` body-only steps, and so does any call that
+        stack's KV cache (the start_loc > (0, 0) prefill, :235-239; that restart costs `pos` body-only steps, or with
+        prefix_mode = 'one_pass' one pass over the prefix as in the reference, and so does any call that
         finds the engine rebuilt, the parameters pushed again or `amp` changed since the previous one) -- and a call with d > 0 must
         follow (h, w, d - 1).  `model_aux` and `cond` are read when a sequence starts; only the code of the step before is re-read
         from `xs` at a continuing call (the reference re-embeds all of `xs` every time).  `xs` holds
@@ -228,9 +251,13 @@ class RQTransformer(Stage2Model):
             c = self._cond(cond, B, xs.device)
             if c is None:
                 c = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=xs.device)
+            one_pass = self._prefix_one_pass()
             eng.step_begin(full.contiguous(), c, cbs)
-            for p in range(pos):
-                eng.step_logits(p, -1)                 # given codes: body KV cache only
+            if one_pass and pos >= 1:
+                eng.step_prefill(pos)                  # given codes: body KV cache only, in one pass (prefix_mode)
+            else:
+                for p in range(pos):
+                    eng.step_logits(p, -1)             # given codes: body KV cache only
         elif d > 0:
             eng.step_set_code(pos, d - 1, xs[:, h, w, d - 1].to(torch.long).contiguous())
         elif pos > 0:
@@ -361,7 +388,10 @@ class RQTransformer(Stage2Model):
         row b, whatever the other images ask for, and one set of captured graphs serves every setting.  Inside ``with
         self.seeds(s)`` image b draws from the Philox stream of seed s[b] instead of the device generator (see seeds()).
         Inside ``with self.return_log_probs():`` the call returns ``(codes, SampleLogProbs(draw, model, None))`` -- the codes are those
-        of the plain call (see return_log_probs())."""
+        of the plain call (see return_log_probs()).
+        ``self.prefix_mode = 'one_pass'``: the given leading positions (before `start_loc`, or a leading run kept in every image) fill
+        the KV cache in one pass instead of one step each (see __init__); the codes then differ from the stepped mode's wherever a draw
+        was close -- GEMM tiles differ, filters and Philox counters are the same."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
@@ -372,7 +402,7 @@ class RQTransformer(Stage2Model):
         top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
-        eng = self._eng(amp)                            # amp=True: the fp16 build of the engine (the reference's fp16 autocast)
+        eng = self._sampling_eng(amp)                   # amp=True: the fp16 build of the engine (the reference's fp16 autocast)
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
         c = self._cond(cond, B, device)
@@ -559,7 +589,7 @@ class RQTransformer(Stage2Model):
                              'available with the default sampler')
         if self.sampler == 'torch' and not cached:
             raise NotImplementedError("sampler='torch' steps the cached engine; cached=False is available with the default sampler")
-        eng = self._eng(amp)
+        eng = self._sampling_eng(amp)
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
         c = self._cond(cond, B, device)
@@ -618,7 +648,7 @@ class RQTransformer(Stage2Model):
         device = partial_sample.device
         if uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
             raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
-        eng = self._eng(amp)
+        eng = self._sampling_eng(amp)
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
         c, u = self._cond(cond, B, device), self._cond(uncond, B, device)
@@ -741,7 +771,15 @@ class RQTransformer(Stage2Model):
         if active is not None:                         # keep_mask: nothing runs after the last position that draws a code
             drawn = active.any(dim=1).nonzero()
             n_pos = int(drawn[-1]) + 1 if len(drawn) else 0
-        for pos in range(n_pos):
+        first = 0
+        if self._prefix_one_pass():                    # the given leading positions in one pass (rqamd_rqt_step_prefill), as the engine's own loop
+            while first < n_pos and (first < start or (active is not None and not active[first].any())):
+                first += 1
+            if 1 <= first < n_pos:
+                eng.step_prefill(first)
+            else:
+                first = 0
+        for pos in range(first, n_pos):
             if pos < start or (active is not None and not active[pos].any()):
                 eng.step_logits(pos, -1)               # given codes: body KV cache only
                 continue
