@@ -145,6 +145,27 @@ int rqamd_sample_logits_logp(const float* logits, const float* logits_u, int row
                              const float* row_temperature, const int* row_top_k, const float* row_top_p,
                              const float* row_gscale, const uint64_t* row_seeds, uint64_t seed, uint64_t offset,
                              int64_t* samples_out, float* draw_logp_out, int* row_flags, void* stream);
+/* Min-p and locally typical sampling (not in the reference); additive, ABI v7.  The arguments of rqamd_sample_logits_logp (the four
+ * forms of the sampler), two more filters, and probs_out / draw_logp_out each optional (at least one of samples_out and probs_out;
+ * draw_logp_out needs samples_out).  Per row, each stage acts on the renormalised output of the stage before it: guidance and
+ * temperature, top-k, NaN scrub and softmax, top-p -- all as in rqamd_sample_logits -- then
+ *   min-p    (0 < min_p <= 1): drop every code whose probability is below min_p times the largest; the leader always stays;
+ *   typical  (0 <= typical_p < 1): over the codes with q > 0, H = -sum q log q and a_i = |-log q_i - H|; the codes in ascending order
+ *            of a (ties: lowest vocabulary index first) up to and including the first whose inclusive cumulative mass reaches
+ *            typical_p are kept -- the inclusive rule of top-p; typical_p = 0 keeps the first code of that order;
+ * then one draw by the exponential race on the Philox counter of rqamd_sample_logits.  min_p <= 0: min-p off; typical_p < 0 or >= 1:
+ * typical off.  A non-finite scalar, or min_p > 1, is RQAMD_ERR_INVALID with nothing written.  row_min_p / row_typical_p: DEVICE arrays
+ * of `rows` entries with row_temperature, each or NULL (NULL: the scalar for every row); they are not validated, like the other
+ * per-row arrays.  A row with both filters off is drawn -- samples_out, probs_out, draw_logp_out, row_flags -- bit for bit as the
+ * existing entry points draw it, by the kernel their class rule selects; a row with either on never takes the streaming kernel, and
+ * the register kernel hands rows back to the general one exactly where it does today.  probs_out holds the distribution after all
+ * stages; draw_logp_out[r] the log of the drawn code's probability in it (+0.0 where one code survives). */
+int rqamd_sample_logits_trunc(const float* logits, const float* logits_u, int rows, int vocab,
+                              float temperature, int top_k, float top_p, float min_p, float typical_p, float guidance_scale,
+                              const float* row_temperature, const int* row_top_k, const float* row_top_p,
+                              const float* row_min_p, const float* row_typical_p,
+                              const float* row_gscale, const uint64_t* row_seeds, uint64_t seed, uint64_t offset,
+                              int64_t* samples_out, float* probs_out, float* draw_logp_out, int* row_flags, void* stream);
 
 /* ---- RQ-VAE encoder / decoder engine -------------------------------------------------------
  * Handle = packed bf16 weights + activation workspace for Encoder/Decoder (modules.py:10-202),
@@ -301,6 +322,16 @@ int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const uint8_t* k
  * The values are written into the handle's workspace and copied out next to codes_out, so captured graphs never hold a caller's
  * pointer.  Armed calls replay graph sets of their own: alternating armed and unarmed calls recaptures nothing. */
 int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* model_logp_out, float* model_logp_uncond_out);
+/* Min-p and locally typical sampling in the engine (the stages of rqamd_sample_logits_trunc); additive, ABI v7.  Arms the NEXT
+ * rqamd_rqt_sample, _masked, _guided or _rows call on the handle; that call consumes the arming whether it succeeds or fails, and
+ * reads the arrays: HOST arrays of D values (one per depth), or -- per_image = 1, valid in front of rqamd_rqt_sample_rows only, else
+ * that call returns RQAMD_ERR_INVALID -- of batch * D values, image-major.  Either pointer NULL: that filter is off; both NULL
+ * disarms.  A non-finite value or a min_p above 1 makes the armed call RQAMD_ERR_INVALID.  It combines freely with
+ * rqamd_rqt_sample_logp: draw is then the log of the probability after all stages.  A scalar call whose every value is off is the
+ * unarmed call; a depth whose two values are off launches what it launches unarmed.  Calls with a filter in effect replay graph
+ * sets of their own (scalar values are part of their key, per-image values live in tables of the handle and a new set of values
+ * replays the same graphs): alternating armed and unarmed calls recaptures nothing. */
+int rqamd_rqt_sample_trunc(rqamd_rqt* h, const float* min_p, const float* typical_p, int per_image);
 /* *captures = the number of position graphs this handle has captured so far (every form of sampling); a call that replays only
  * leaves it unchanged. */
 int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures);

@@ -89,11 +89,14 @@ struct rqamd_rqt {
     int* row_tk;                // [rows][D]
     float* row_tp;              // [rows][D]
     uint64_t* row_seed;         // [rows]
-    std::vector<char> row_host; // host staging of the five arrays: outlives the asynchronous copies of the call that filled it
+    float *row_mp, *row_typ;    // [rows][D] min-p / typical values of a per-row call armed by rqamd_rqt_sample_trunc (both filled, off values where a filter is not given)
+    std::vector<char> row_host; // host staging of the arrays: outlives the asynchronous copies of the call that filled it
     // log-probabilities of an armed call (rqamd_rqt_sample_logp), laid out like xs: filled before the position loop (draw 0, model NaN), written
     // by the LOGP samplers and the step form of log_prob_kernel, copied out next to the codes -- the captured graphs hold these addresses
     float *logp_draw, *logp_model;      // [rows][HW][D]
     struct LogpArm { float *draw, *model, *model_u; bool on() const { return draw || model || model_u; } } arm = {};   // outputs of the next sampling call
+    // the arming of rqamd_rqt_sample_trunc: HOST arrays, read by the next sampling call (D entries each, or batch * D image-major)
+    struct TruncArm { const float *min_p, *typical_p; int per_image; bool on() const { return min_p || typical_p; } } tarm = {};
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -114,10 +117,13 @@ struct rqamd_rqt {
     // codebooks, stream and the guided flag only, and a call with other values replays what is there.  Scalar and per-row families
     // never invalidate each other.  Armed calls (rqamd_rqt_sample_logp: other sampler kernels and one more launch per step) are six
     // more families, gkey[6] .. gkey[11] and sets [12] .. [23], in the same order: alternating armed and unarmed calls recaptures nothing.
+    // Calls with min-p / typical sampling in effect (rqamd_rqt_sample_trunc: other sampler kernels at the depths with a filter on) are
+    // all twelve once more, gkey[12] .. gkey[23] and sets [24] .. [47].  Their scalar values are in the key next to tk / tp (mp, typ:
+    // zero in every other family's key); per-image values are in h->row_mp / h->row_typ and in no key.
     static constexpr int NGRAPH = 33;
-    static constexpr int NFAM = 12;
+    static constexpr int NFAM = 24;
     hipGraphExec_t gexec[2 * NFAM][NGRAPH] = {};
-    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; } gkey[NFAM];
+    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; } gkey[NFAM];
     bool gkey_set[NFAM] = {}, gstale[NFAM] = {};
     bool gvalid = false;
     int64_t n_capture = 0;     // position graphs captured over the life of the handle (rqamd_rqt_graph_captures)
@@ -435,7 +441,7 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + al(brows * V * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
                    + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4)
                    + al(brows * h->HW * h->D)
-                   + 2 * al(brows * 4) + 2 * al(brows * h->D * 4) + al(brows * 8) + 2 * al(brows * h->HW * h->D * 4);
+                   + 2 * al(brows * 4) + 4 * al(brows * h->D * 4) + al(brows * 8) + 2 * al(brows * h->HW * h->D * 4);
     RQ_TRY(h->ws.reserve(total));
     char* p = (char*)h->ws.p;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
@@ -451,6 +457,7 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     h->row_T = (float*)take(brows * 4); h->row_gs = (float*)take(brows * 4);
     h->row_tk = (int*)take(brows * h->D * 4); h->row_tp = (float*)take(brows * h->D * 4);
     h->row_seed = (uint64_t*)take(brows * 8);
+    h->row_mp = (float*)take(brows * h->D * 4); h->row_typ = (float*)take(brows * h->D * 4);
     h->logp_draw = (float*)take(brows * h->HW * h->D * 4); h->logp_model = (float*)take(brows * h->HW * h->D * 4);
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
     const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
@@ -607,6 +614,9 @@ struct StepCtx {
     bool per_row;          // rqamd_rqt_sample_rows: the sampler reads temperature / top_k / top_p (and gscale when guided) of each row from
     bool row_seeds;        //   h->row_*, and with row_seeds the Philox key from h->row_seed; the scalars above are unused
     bool logp;             // armed call (rqamd_rqt_sample_logp): the LOGP samplers write h->logp_draw, a step log_prob launch h->logp_model
+    bool trunc;            // min-p / typical sampling in effect (rqamd_rqt_sample_trunc): scalar calls read min_p[d] / typical_p[d] (host arrays of
+    const float* min_p;    //   D values, off values where a filter is not given: a depth with both off launches what it launches unarmed); per-row
+    const float* typical_p; //  calls read h->row_mp / h->row_typ at every depth
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -706,6 +716,10 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
             if (c.row_seeds) { s.row_seeds = h->row_seed; s.rng = nullptr; }      // key row_seed[b], counter 0 + slot (s.offset is 0)
         }
         if (c.logp) s.logp_out = h->logp_draw;
+        if (c.trunc) {
+            if (c.per_row) { s.row_min_p = h->row_mp; s.row_typical_p = h->row_typ; }
+            else { s.min_p = c.min_p[d]; s.typical_p = c.typical_p[d]; }
+        }
         RQ_TRY(rq_launch_sample(s, st));
         if (c.logp) {
             // log_softmax(raw logits of the row)[code] for every row of the step (both twins of a guided pair), drawn and kept codes alike:
@@ -811,7 +825,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         RQ_LAUNCH(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->logp_model, __builtin_nanf(""), n);
         RQ_TRY(rq_check_launch("fill_f32_kernel"));
     }
-    const int fam = (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
+    const int fam = (c.trunc ? 12 : 0) + (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = n0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
@@ -877,9 +891,9 @@ static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
     h->arm = {};
     return a;
 }
-struct ArmGuard {          // an entry point that returns before sample_impl still consumes the arming
+struct ArmGuard {          // an entry point that returns before sample_impl still consumes the armings
     rqamd_rqt* h;
-    ~ArmGuard() { if (h) h->arm = {}; }
+    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; } }
 };
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
@@ -891,12 +905,35 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     hipStream_t st = (hipStream_t)stream;
     h->step_on = false;
     const rqamd_rqt::LogpArm arm = take_arm(h);        // (consumed here at the latest: the entry points take it before their own checks)
+    const rqamd_rqt::TruncArm tarm = h->tarm;
+    h->tarm = {};
     if (arm.model_u && !guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: model_logp_uncond_out armed for an unguided call");
+    // min-p / typical values of the call: tr_mp / tr_typ hold D values (scalar calls) or batch * D (per-row calls: a D-entry arming is
+    // repeated for every image), off values where a filter is not given.  Scalar calls whose every value is off are unarmed calls.
+    if (tarm.per_image && !rp) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_trunc: per-image values armed in front of a call without per-row parameters");
+    std::vector<float> tr_mp, tr_typ;
+    bool trunc = false;
+    if (tarm.on()) {
+        const size_t n = (rp ? (size_t)batch : 1) * h->D;
+        tr_mp.assign(n, 0.f); tr_typ.assign(n, -1.f);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t j = tarm.per_image ? i : i % h->D;
+            if (tarm.min_p) tr_mp[i] = tarm.min_p[j];
+            if (tarm.typical_p) tr_typ[i] = tarm.typical_p[j];
+            if (!(tr_mp[i] - tr_mp[i] == 0.f) || tr_mp[i] > 1.0f) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_trunc: min_p[%d] must be finite and at most 1", (int)j);
+            if (!(tr_typ[i] - tr_typ[i] == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_trunc: typical_p[%d] must be finite", (int)j);
+            if (!(tr_mp[i] > 0.f)) tr_mp[i] = 0.f;                                     // one off value each: equal keys for equal behaviour
+            if (!(tr_typ[i] >= 0.f && tr_typ[i] < 1.0f)) tr_typ[i] = -1.f;
+            trunc = trunc || tr_mp[i] > 0.f || tr_typ[i] >= 0.f;
+        }
+        if (rp) trunc = true;          // per-row: the tables are read on the device, whatever they hold
+    }
     const int rows = guided ? 2 * batch : batch;
     RQ_TRY(ensure_batch(h, rows));
     StepCtx c{};
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
     c.guided = guided; c.Bs = batch; c.gscale = gscale; c.logp = arm.on();
+    c.trunc = trunc; c.min_p = tr_mp.data(); c.typical_p = tr_typ.data();
     if (rp) {
         // per-row values: host arrays -> one staging block owned by the handle -> h->row_* by asynchronous copies ahead of the position
         // loop on the same stream, outside any capture.  The caller's arrays are read before this function returns; the staging block
@@ -904,7 +941,7 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
         // for the codes of one call before they make the next).
         c.per_row = true; c.row_seeds = rp->seeds != nullptr;
         const size_t nB = (size_t)batch, nD = nB * h->D;
-        const size_t oT = 0, oG = oT + nB * 4, oK = oG + nB * 4, oP = oK + nD * 4, oS = (oP + nD * 4 + 7) & ~(size_t)7, total = oS + nB * 8;
+        const size_t oT = 0, oG = oT + nB * 4, oK = oG + nB * 4, oP = oK + nD * 4, oM = oP + nD * 4, oY = oM + nD * 4, oS = (oY + nD * 4 + 7) & ~(size_t)7, total = oS + nB * 8;
         RQ_HIP(hipStreamSynchronize(st));
         h->row_host.resize(total);
         char* hb = h->row_host.data();
@@ -913,11 +950,16 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
         memcpy(hb + oK, rp->top_k, nD * 4);
         memcpy(hb + oP, rp->top_p, nD * 4);
         if (rp->seeds) memcpy(hb + oS, rp->seeds, nB * 8);
+        if (trunc) { memcpy(hb + oM, tr_mp.data(), nD * 4); memcpy(hb + oY, tr_typ.data(), nD * 4); }
         RQ_HIP(hipMemcpyAsync(h->row_T, hb + oT, nB * 4, hipMemcpyHostToDevice, st));
         if (guided) RQ_HIP(hipMemcpyAsync(h->row_gs, hb + oG, nB * 4, hipMemcpyHostToDevice, st));
         RQ_HIP(hipMemcpyAsync(h->row_tk, hb + oK, nD * 4, hipMemcpyHostToDevice, st));
         RQ_HIP(hipMemcpyAsync(h->row_tp, hb + oP, nD * 4, hipMemcpyHostToDevice, st));
         if (rp->seeds) RQ_HIP(hipMemcpyAsync(h->row_seed, hb + oS, nB * 8, hipMemcpyHostToDevice, st));
+        if (trunc) {
+            RQ_HIP(hipMemcpyAsync(h->row_mp, hb + oM, nD * 4, hipMemcpyHostToDevice, st));
+            RQ_HIP(hipMemcpyAsync(h->row_typ, hb + oY, nD * 4, hipMemcpyHostToDevice, st));
+        }
     }
     // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
     // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
@@ -927,8 +969,9 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     if (!rp) {             // (per-row calls: no parameter value is in a captured launch, so none is in the key)
         k.T = temperature; k.gs = guided ? gscale : 0.f;
         for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
+        if (trunc) for (int d = 0; d < h->D; ++d) { k.mp[d] = tr_mp[d]; k.typ[d] = tr_typ[d]; }
     }
-    const int fam = (arm.on() ? 6 : 0) + (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
+    const int fam = (trunc ? 12 : 0) + (arm.on() ? 6 : 0) + (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
     if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
@@ -1039,6 +1082,15 @@ extern "C" int rqamd_rqt_sample_rows(rqamd_rqt* h, const int64_t* partial, const
 extern "C" int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* model_logp_out, float* model_logp_uncond_out) {
     if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: null handle");
     h->arm = rqamd_rqt::LogpArm{draw_logp_out, model_logp_out, model_logp_uncond_out};
+    return RQAMD_OK;
+}
+
+// Arms the next rqamd_rqt_sample / _masked / _guided / _rows call on the handle with min-p and / or locally typical sampling
+// (include/rqamd.h): HOST arrays, read by that call -- D values, or batch * D image-major with per_image = 1 (in front of
+// rqamd_rqt_sample_rows only).  Either NULL: that filter is off; both NULL disarms.
+extern "C" int rqamd_rqt_sample_trunc(rqamd_rqt* h, const float* min_p, const float* typical_p, int per_image) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_trunc: null handle");
+    h->tarm = rqamd_rqt::TruncArm{min_p, typical_p, (min_p || typical_p) && per_image ? 1 : 0};
     return RQAMD_OK;
 }
 

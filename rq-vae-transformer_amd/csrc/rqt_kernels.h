@@ -105,7 +105,20 @@ struct SampleArgs {
     // (rqt_sample_logp.hip), which also write log(probability of the drawn code in the distribution the draw was made from) to
     // logp_out[row * out_stride + slot] -- addressed like `out`, no mirror; kept codes write nothing.  Same codes as with null.
     float* logp_out;
+    // min-p and locally typical sampling (rqamd_sample_logits_trunc / rqamd_rqt_sample_trunc): a row with either filter on takes the
+    // TRUNC instantiations (rqt_sample_trunc.hip), which run the two stages after top-p, each on the renormalised output of the stage
+    // before it.  Off values (the defaults here) and null tables: the kernels above, bit for bit.  The tables are read at
+    // [row * D + d] like row_top_p and need row_temperature; a null table leaves the scalar in force for every row.
+    float min_p = 0.f;              // <= 0: off; else drop q_i < min_p * max q
+    float typical_p = -1.f;         // < 0 or >= 1: off; else the prefix of the |surprisal - entropy| order that reaches this mass
+    const float* row_min_p = nullptr;       // [rows * D], or null
+    const float* row_typical_p = nullptr;   // [rows * D], or null
 };
+// is a filter of the TRUNC instantiations in effect (scalars), or could one be (tables)?
+static inline bool rq_sample_trunc_on(const SampleArgs& a) {
+    return a.row_min_p || a.row_typical_p || a.min_p > 0.f || (a.typical_p >= 0.f && a.typical_p < 1.0f);
+}
+int rq_launch_sample_trunc(const SampleArgs& a, hipStream_t s);     // rqt_sample_trunc.hip
 
 int rq_launch_guide_logits(const float* c, const float* u, int rows, int V, float scale, float* out, hipStream_t s);
 int rq_launch_resid_ln(const ResidLnArgs& a, hipStream_t s);

@@ -18,8 +18,9 @@ static __device__ __forceinline__ float rq_u01(uint32_t r) { return fmaf((float)
 // changes the code the compiler emits for sample_topk_kernel<false> (a module-level effect: register allocation of its top-k search),
 // and the unguided instruction stream is to stay as it is.  rqt_sample_rows.hip does the same with RQ_SAMPLE_ROWS_TU for the per-row
 // instantiations (ROWS = true, unguided and guided), for the same reason, and rqt_sample_logp.hip with RQ_SAMPLE_LOGP_TU for the
-// instantiations that also report the log-probability of the draw (LOGP = true, all four of the above).
-#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU)
+// instantiations that also report the log-probability of the draw (LOGP = true, all four of the above), and rqt_sample_trunc.hip with
+// RQ_SAMPLE_TRUNC_TU for the ones with the min-p and typical stages (TRUNC = true, all four once more).
+#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU)
 #define RQ_SAMPLE_ONLY_TU 1
 #endif
 #ifndef RQ_SAMPLE_ONLY_TU
@@ -1462,21 +1463,35 @@ static __device__ __forceinline__ float guide_logit(float c, float u, float s) {
 // makes row r of a per-row call bit-identical to row r of a scalar call with r's values.  All loads here are uniform over the
 // workgroup (addresses depend on blockIdx alone).
 enum { SMP_ROW_GUMBEL = 0, SMP_ROW_TOPK = 1, SMP_ROW_GENERAL = 2 };
+// TRUNC (rqt_sample_trunc.hip): a row whose min-p or typical filter is on never streams; with both off its class is today's
+static __device__ __forceinline__ bool trunc_min_p_on(float m) { return m > 0.f; }
+static __device__ __forceinline__ bool trunc_typical_on(float t) { return t >= 0.f && t < 1.0f; }
+template <bool TRUNC = false>
 static __device__ __forceinline__ int sample_row_class(const SampleArgs& p, int row) {
     const int k = p.row_top_k[(long)row * p.D + p.d];
     const float tp = p.row_top_p[(long)row * p.D + p.d];
     const bool k_on = k > 0 && k < p.V;
-    if (!k_on && (tp < 0.f || tp >= 1.0f) && !p.probs_out && p.out) return SMP_ROW_GUMBEL;
+    bool t_on = false;
+    if (TRUNC) {
+        t_on = trunc_min_p_on(p.row_min_p ? p.row_min_p[(long)row * p.D + p.d] : p.min_p) ||
+               trunc_typical_on(p.row_typical_p ? p.row_typical_p[(long)row * p.D + p.d] : p.typical_p);
+    }
+    if (!k_on && (tp < 0.f || tp >= 1.0f) && !t_on && !p.probs_out && p.out) return SMP_ROW_GUMBEL;
     if (k_on && p.V <= SMP_T * SMP_VPT && p.V % 4 == 0 && p.redo) return SMP_ROW_TOPK;
     return SMP_ROW_GENERAL;
 }
 // the row's own values into the kernel's copy of the arguments: from here on the scalar code runs unchanged
+template <bool TRUNC = false>
 static __device__ __forceinline__ void sample_row_params(SampleArgs& p, int row) {
     p.temperature = p.row_temperature[row];
     p.top_k = p.row_top_k[(long)row * p.D + p.d];
     p.top_p = p.row_top_p[(long)row * p.D + p.d];
     if (p.row_gscale) p.gscale = p.row_gscale[row];
     if (p.row_seeds) { p.rng = nullptr; p.seed = p.row_seeds[row]; }      // (p.offset stays: 0 in the engine, the caller's elsewhere)
+    if (TRUNC) {
+        if (p.row_min_p) p.min_p = p.row_min_p[(long)row * p.D + p.d];
+        if (p.row_typical_p) p.typical_p = p.row_typical_p[(long)row * p.D + p.d];
+    }
 }
 
 // The three samplers are templates on GUIDED.  <false>: the unguided kernels, whose instruction stream the parameter leaves as it was.
@@ -1489,9 +1504,131 @@ static __device__ __forceinline__ void sample_store(const SampleArgs& p, int row
     if (GUIDED && p.out_mirror) p.out[o + p.out_mirror] = (int64_t)code;
 }
 
+// TRUNC (rqt_sample_trunc.hip): min-p, then locally typical sampling, on the renormalised probabilities q that top-p leaves.
+//   min-p    drop q_i < fl(min_p * max q); the leader stays whatever min_p is; q <- q / kept.
+//   typical  over q_i > 0: H = -sum q_i log q_i, a_i = |-log q_i - H|.  log q_i is logf(q_i) of the renormalised probability itself, not
+//            x'_i - max - log z: after top-p and min-p the normaliser is a product of three sums, and logf is exact to an ulp on every
+//            positive float, subnormal ones included (a sharp softmax leaves them; their surprisal is ~ 87 - 103, their q_i log q_i
+//            below 1e-36, so H stays finite and at most log V for every row with a live entry; one live entry: q = 1, H = 0, a = 0).
+//            The order is (a_i, index) ascending, a_i compared by the bit pattern of the non-negative float.  c = the largest pattern
+//            with mass{a < c} < p, found by a 31-step bitwise search with one block reduction per step (the cadence of the top-p
+//            search): every entry below c stays, the entries at c are the boundary ties.  Ties of a_i need not have equal q_i (the two
+//            sides of H), so the cut among them is the largest index ci with mass{a < c or (a = c and index < ci)} < p, one more
+//            bitwise search over the index (run only where there is more than one tie): ties up to ci stay.  typical_p = 0 is searched
+//            as the smallest positive p, as top_p = 0 is: the first token of the order.  A row whose whole mass sums below p in fp32
+//            keeps everything (c ends at 0x7fffffff).  Dead and absent entries carry the key 0xffffffff, above every candidate.
+// The general form: q in LDS (sx), the keys in 64 registers per thread while V <= 16384 and formed again from sx at every step beyond
+// (no LDS of their own: the occupancy of 2 workgroups per CU stays).  The register form is trunc_regs below.
+static __device__ __forceinline__ unsigned typical_key(float q, float H) {
+    return q > 0.f ? __float_as_uint(fabsf(-logf(q) - H)) : 0xffffffffu;
+}
+static __device__ __forceinline__ void trunc_lds(const SampleArgs& p, float* sx, int V, float* red, float* red2) {
+    const int tid = threadIdx.x;
+    if (trunc_min_p_on(p.min_p)) {
+        float m = 0.f;
+        for (int i = tid; i < V; i += SMP_T) m = fmaxf(m, sx[i]);
+        m = blk_max(m, red);
+        const float thr = p.min_p * m;
+        float kept = 0.f;
+        for (int i = tid; i < V; i += SMP_T) {
+            float q = sx[i];
+            if (q < thr && q != m) q = 0.f;
+            sx[i] = q;
+            kept += q;
+        }
+        kept = blk_sum(kept, red);
+        for (int i = tid; i < V; i += SMP_T) sx[i] = sx[i] / kept;
+        rq_syncthreads();
+    }
+    if (trunc_typical_on(p.typical_p)) {
+        const float tp = fmaxf(p.typical_p, 1.17549435e-38f);
+        float h = 0.f;
+        for (int i = tid; i < V; i += SMP_T) { const float q = sx[i]; if (q > 0.f) h += q * logf(q); }
+        const float H = -blk_sum(h, red);
+        const bool in_regs = V <= SMP_T * SMP_VPT;
+        unsigned ab[SMP_VPT];
+#pragma unroll
+        for (int k = 0; k < SMP_VPT; ++k) {
+            const int i = tid + k * SMP_T;
+            ab[k] = (in_regs && i < V) ? typical_key(sx[i], H) : 0xffffffffu;
+        }
+        // mass of the entries that come before (c, ci) in the (a, index) order
+        auto mass_before = [&](unsigned c, unsigned ci) -> float {
+            float g = 0.f;
+            if (in_regs) {
+                float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+#pragma unroll
+                for (int k = 0; k < SMP_VPT; k += 4) {
+                    const unsigned i = (unsigned)(tid + k * SMP_T);
+                    if (ab[k] < c || (ab[k] == c && i < ci)) g0 += sx[i];
+                    if (ab[k + 1] < c || (ab[k + 1] == c && i + SMP_T < ci)) g1 += sx[i + SMP_T];
+                    if (ab[k + 2] < c || (ab[k + 2] == c && i + 2 * SMP_T < ci)) g2 += sx[i + 2 * SMP_T];
+                    if (ab[k + 3] < c || (ab[k + 3] == c && i + 3 * SMP_T < ci)) g3 += sx[i + 3 * SMP_T];
+                }
+                g = (g0 + g1) + (g2 + g3);
+            } else {
+                for (int i = tid; i < V; i += SMP_T) {
+                    const float q = sx[i];
+                    const unsigned a = typical_key(q, H);
+                    if (a < c || (a == c && (unsigned)i < ci)) g += q;
+                }
+            }
+            return g;
+        };
+        unsigned cur = 0;
+        for (int bit = 30; bit >= 0; --bit) {
+            const unsigned cand = cur | (1u << bit);
+            if (blk_sum_pp(mass_before(cand, 0u), red2, bit) < tp) cur = cand;
+        }
+        float nt = 0.f;                                  // ties at the boundary (a count below 2^24: exact in fp32)
+        if (in_regs) {
+#pragma unroll
+            for (int k = 0; k < SMP_VPT; ++k) nt += ab[k] == cur ? 1.f : 0.f;
+        } else {
+            for (int i = tid; i < V; i += SMP_T) nt += typical_key(sx[i], H) == cur ? 1.f : 0.f;
+        }
+        nt = blk_sum(nt, red);
+        unsigned cut = 0xffffffffu;                      // ties with index <= cut survive
+        if (nt > 1.f) {                                  // uniform
+            unsigned ci = 0;
+            for (int bit = 15; bit >= 0; --bit) {        // V <= 36000 < 2^16
+                const unsigned cand = ci | (1u << bit);
+                if (blk_sum_pp(mass_before(cur, cand), red2, bit) < tp) ci = cand;
+            }
+            cut = ci;
+        }
+        rq_syncthreads();
+        float kept = 0.f;
+        if (in_regs) {
+#pragma unroll
+            for (int k = 0; k < SMP_VPT; ++k) {
+                const int i = tid + k * SMP_T;
+                if (i < V) {
+                    float q = sx[i];
+                    if (!(ab[k] < cur || (ab[k] == cur && (unsigned)i <= cut))) q = 0.f;
+                    sx[i] = q;
+                    kept += q;
+                }
+            }
+        } else {
+            for (int i = tid; i < V; i += SMP_T) {
+                float q = sx[i];
+                const unsigned a = typical_key(q, H);
+                if (!(a < cur || (a == cur && (unsigned)i <= cut))) q = 0.f;
+                sx[i] = q;
+                kept += q;
+            }
+        }
+        kept = blk_sum(kept, red);
+        for (int i = tid; i < V; i += SMP_T) sx[i] = sx[i] / kept;
+        rq_syncthreads();
+    }
+}
+
 // LOGP (rqt_sample_logp.hip): the log of the probability the drawn code had in the distribution the draw was made from -- after
 // guidance, temperature, top-k, top-p and renormalisation -- goes to p.logp_out, addressed like p.out (no mirror).  <.., false>: as before.
-template <bool GUIDED, bool ROWS = false, bool LOGP = false>
+// TRUNC kernels are built with LOGP = true alone and write where p.logp_out is given.
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1503,9 +1640,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (ROWS) {                                // the general rows, and the register kernel's rows that it handed back
-        const int cls = sample_row_class(p, row);
+        const int cls = sample_row_class<TRUNC>(p, row);
         if (cls == SMP_ROW_GUMBEL || (cls == SMP_ROW_TOPK && !p.redo[row])) return;
-        sample_row_params(p, row);
+        sample_row_params<TRUNC>(p, row);
     }
     if (!ROWS && p.redo && !p.redo[row]) return;        // second pass after sample_topk_kernel: only the rows it handed back
     const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
@@ -1637,6 +1774,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
         for (int i = tid; i < V; i += SMP_T) sx[i] = sx[i] / kept;
         rq_syncthreads();
     }
+    if (TRUNC) trunc_lds(p, sx, V, red, red2);
 
     if (p.probs_out)
         for (int i = tid; i < V; i += SMP_T) p.probs_out[(long)row * V + i] = sx[i];
@@ -1676,7 +1814,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
             if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
         if (besti >= V) besti = 0;
         sample_store<GUIDED>(p, row, slot, besti);
-        if (LOGP) p.logp_out[(long)row * p.out_stride + slot] = logf(sx[besti]);     // the probability the race used
+        if (LOGP && (!TRUNC || p.logp_out)) p.logp_out[(long)row * p.out_stride + slot] = logf(sx[besti]);     // the probability the race used
     }
 }
 
@@ -1723,8 +1861,80 @@ static __device__ __forceinline__ int blk_count_pp(int wave_cnt, SmpShared& sh, 
     return (sh.cnt[parity & 1][0] + sh.cnt[parity & 1][1]) + (sh.cnt[parity & 1][2] + sh.cnt[parity & 1][3]);
 }
 
+// The register form of trunc_lds (see there): the same two stages on the NV probabilities a thread holds after top-p; absent and
+// dropped entries are q = 0.  The 31-step search over the keys and the 15-step search over the index (V <= 16384 < 2^15) reduce
+// through blk_sum_pp, as the top-p search does.
+template <int NV, typename IdxF>
+static __device__ __forceinline__ void trunc_regs(const SampleArgs& p, float (&q)[NV], IdxF idx_of, SmpShared& sh) {
+    if (trunc_min_p_on(p.min_p)) {
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) m = fmaxf(m, q[k]);
+        m = blk_max(m, sh.red);
+        const float thr = p.min_p * m;
+        float kept = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            if (q[k] < thr && q[k] != m) q[k] = 0.f;
+            kept += q[k];
+        }
+        kept = blk_sum(kept, sh.red);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) q[k] = q[k] / kept;
+    }
+    if (trunc_typical_on(p.typical_p)) {
+        const float tp = fmaxf(p.typical_p, 1.17549435e-38f);
+        float h = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) if (q[k] > 0.f) h += q[k] * logf(q[k]);
+        const float H = -blk_sum(h, sh.red);
+        unsigned ab[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) ab[k] = typical_key(q[k], H);
+        auto mass_before = [&](unsigned c, unsigned ci) -> float {
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; k += 4) {
+                g0 += (ab[k] < c || (ab[k] == c && (unsigned)idx_of(k) < ci)) ? q[k] : 0.f;
+                g1 += (ab[k + 1] < c || (ab[k + 1] == c && (unsigned)idx_of(k + 1) < ci)) ? q[k + 1] : 0.f;
+                g2 += (ab[k + 2] < c || (ab[k + 2] == c && (unsigned)idx_of(k + 2) < ci)) ? q[k + 2] : 0.f;
+                g3 += (ab[k + 3] < c || (ab[k + 3] == c && (unsigned)idx_of(k + 3) < ci)) ? q[k + 3] : 0.f;
+            }
+            return (g0 + g1) + (g2 + g3);
+        };
+        unsigned cur = 0;
+        for (int bit = 30; bit >= 0; --bit) {
+            const unsigned cand = cur | (1u << bit);
+            if (blk_sum_pp(mass_before(cand, 0u), sh.red2, bit) < tp) cur = cand;
+        }
+        int nt = 0;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) nt += ab[k] == cur ? 1 : 0;
+        int ntie;
+        (void)blk_excl_scan(nt, sh.redi, &ntie);
+        unsigned cut = 0xffffffffu;                      // ties with index <= cut survive
+        if (ntie > 1) {                                  // uniform
+            unsigned ci = 0;
+            for (int bit = 14; bit >= 0; --bit) {
+                const unsigned cand = ci | (1u << bit);
+                if (blk_sum_pp(mass_before(cur, cand), sh.red2, bit) < tp) ci = cand;
+            }
+            cut = ci;
+        }
+        float kept = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            if (!(ab[k] < cur || (ab[k] == cur && (unsigned)idx_of(k) <= cut))) q[k] = 0.f;
+            kept += q[k];
+        }
+        kept = blk_sum(kept, sh.red);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) q[k] = q[k] / kept;
+    }
+}
+
 // softmax -> top-p -> renormalise -> (probs_out) -> draw, on NV scaled logits per thread (absent entries: idx < 0)
-template <bool GUIDED, bool ROWS, bool LOGP, int NV, typename IdxF>
+template <bool GUIDED, bool ROWS, bool LOGP, bool TRUNC, int NV, typename IdxF>
 static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&q)[NV], IdxF idx_of, int row, SmpShared& sh) {
     const int tid = threadIdx.x, V = p.V;
     const float NEG_INF = -__int_as_float(0x7f800000);
@@ -1810,6 +2020,7 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
 #pragma unroll
         for (int k = 0; k < NV; ++k) q[k] = q[k] / kept;
     }
+    if (TRUNC) trunc_regs<NV>(p, q, idx_of, sh);
 
     if (p.probs_out) {
 #pragma unroll
@@ -1852,18 +2063,18 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
             if (sh.red[w] > best || (sh.red[w] == best && sh.redi[w] < besti)) { best = sh.red[w]; besti = sh.redi[w]; if (LOGP) bestq = sh.red2[w]; }
         if (besti >= V) besti = 0;
         sample_store<GUIDED>(p, row, slot, besti);
-        if (LOGP) p.logp_out[(long)row * p.out_stride + slot] = logf(bestq);
+        if (LOGP && (!TRUNC || p.logp_out)) p.logp_out[(long)row * p.out_stride + slot] = logf(bestq);
     }
 }
 
-template <bool GUIDED, bool ROWS = false, bool LOGP = false>
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given (redo[row] is neither written nor read)
     if (ROWS) {                                // rows of another class leave redo[row] alone: the general kernel reads it for this class only
-        if (sample_row_class(p, row) != SMP_ROW_TOPK) return;
-        sample_row_params(p, row);
+        if (sample_row_class<TRUNC>(p, row) != SMP_ROW_TOPK) return;
+        sample_row_params<TRUNC>(p, row);
     }
     const float* lg = p.logits + (long)row * V;
     const int V4 = V >> 2;
@@ -1981,7 +2192,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
         qi[k] = s < total ? sh.idx[s] : -1;
     }
     rq_syncthreads();
-    sample_tail<GUIDED, ROWS, LOGP, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
+    sample_tail<GUIDED, ROWS, LOGP, TRUNC, SMP_CV>(p, q, [&](int k) -> int { return qi[k]; }, row, sh);
 }
 
 // Unfiltered draw (top_k covers the vocabulary, top_p >= 1: the reference's defaults, transformers.py:309-323):
@@ -1992,7 +2203,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
 // LOGP: the streaming pass has no normalisation, so each thread also keeps a running (max, sum of exp) over its scrubbed, scaled values
 // -- the `take` of log_prob_kernel, one rescale per new maximum -- and the winner's own value; the four wavefronts combine them and
 // thread 0 writes x_best - M - logf(S).  expf / logf here, not the one-instruction forms: the result is not rounded to 16 bits afterwards.
-template <bool GUIDED, bool ROWS = false, bool LOGP = false>
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>      // TRUNC: the class rule alone (a filtered row never streams)
 __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
@@ -2000,8 +2211,8 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (ROWS) {
-        if (sample_row_class(p, row) != SMP_ROW_GUMBEL) return;
-        sample_row_params(p, row);
+        if (sample_row_class<TRUNC>(p, row) != SMP_ROW_GUMBEL) return;
+        sample_row_params<TRUNC>(p, row);
     }
     const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     const float* lg = p.logits + (long)row * V;
@@ -2077,43 +2288,53 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
 }
 
 // the launch sequence of one sampling step, for the unguided (this object) or the guided kernels (rqt_sample_guided.hip)
-template <bool GUIDED, bool LOGP = false>
+// TRUNC (rqt_sample_trunc.hip, LOGP = true): the caller has a filter of its own on, so the row never streams
+template <bool GUIDED, bool LOGP = false, bool TRUNC = false>
 static int launch_sample(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!(a.temperature > 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: temperature must be > 0");
     if (GUIDED && !(a.gscale - a.gscale == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: guidance scale must be finite");
+    if (TRUNC) {
+        if (!(a.min_p - a.min_p == 0.f) || a.min_p > 1.0f) return rq_fail(RQAMD_ERR_INVALID, "sampler: min_p must be finite and at most 1");
+        if (!(a.typical_p - a.typical_p == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: typical_p must be finite");
+        if (!(a.min_p > 0.f) && !(a.typical_p >= 0.f && a.typical_p < 1.0f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: neither min_p nor typical_p is on");
+    }
+    if constexpr (!TRUNC) {
     if ((a.top_k <= 0 || a.top_k >= a.V) && (a.top_p < 0.f || a.top_p >= 1.0f) && !a.probs_out && a.out) {
         const auto kern = sample_gumbel_kernel<GUIDED, false, LOGP>;
         RQ_LAUNCH(kern, dim3(a.rows), dim3(256), 0, s, a);
         return rq_check_launch("sample_gumbel_kernel");
     }
+    }
     const size_t smem = (size_t)a.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)sample_kernel<GUIDED, false, LOGP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)sample_kernel<GUIDED, false, LOGP, TRUNC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     SampleArgs b = a;
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch
     if (a.top_k > 0 && a.top_k < a.V && a.V <= SMP_T * SMP_VPT && a.V % 4 == 0 && a.redo && !env_lds_only) {
         // top-k on: register-resident kernel; rows it cannot finish (more than SMP_CAP keys tied into the top k, NaN
         // threshold) are flagged in a.redo and redone by the general kernel, whose other workgroups exit at once
-        const auto kern = sample_topk_kernel<GUIDED, false, LOGP>;
+        const auto kern = sample_topk_kernel<GUIDED, false, LOGP, TRUNC>;
         RQ_LAUNCH(kern, dim3(a.rows), dim3(SMP_T), 0, s, a);
         RQ_TRY(rq_check_launch("sample_topk_kernel"));
     } else {
         b.redo = nullptr;
     }
-    const auto gen = sample_kernel<GUIDED, false, LOGP>;
+    const auto gen = sample_kernel<GUIDED, false, LOGP, TRUNC>;
     RQ_LAUNCH(gen, dim3(a.rows), dim3(SMP_T), smem, s, b);
     return rq_check_launch("sample_kernel");
 }
 
-#if defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU)
+#if defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU)
 // per-row parameters: the three kernels over all rows, each workgroup leaving at once unless the row is of its class (sample_row_class).
 // The streaming kernel cannot write probs_out and the register kernel needs V <= 16384, V % 4 == 0 and the redo workspace: where a
 // kernel can have no rows it is not launched.  The general kernel comes last (it reads the flags the register kernel wrote).  The
 // values are device arrays, so nothing about them is checked here; the kernels trap on none (temperature <= 0 or NaN draws garbage).
-template <bool GUIDED, bool LOGP = false>
+// TRUNC: the rows whose two filters are off take the kernel of their class as today (the streaming kernel with or without LOGP, as
+// a.logp_out says); the register and the general kernel are the LOGP = true builds, which write where a.logp_out is given.
+template <bool GUIDED, bool LOGP = false, bool TRUNC = false>
 static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!a.row_top_k || !a.row_top_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: per-row top_k / top_p missing");
@@ -2121,17 +2342,18 @@ static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch, as in launch_sample
     if (env_lds_only) b.redo = nullptr;
     if (!b.probs_out && b.out) {
-        const auto kern = sample_gumbel_kernel<GUIDED, true, LOGP>;
+        auto kern = sample_gumbel_kernel<GUIDED, true, LOGP, TRUNC>;
+        if constexpr (TRUNC) { if (!b.logp_out) kern = sample_gumbel_kernel<GUIDED, true, false, true>; }
         RQ_LAUNCH(kern, dim3(b.rows), dim3(256), 0, s, b);
         RQ_TRY(rq_check_launch("sample_gumbel_kernel (per row)"));
     }
     if (b.V <= SMP_T * SMP_VPT && b.V % 4 == 0 && b.redo) {
-        const auto kern = sample_topk_kernel<GUIDED, true, LOGP>;
+        const auto kern = sample_topk_kernel<GUIDED, true, LOGP, TRUNC>;
         RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), 0, s, b);
         RQ_TRY(rq_check_launch("sample_topk_kernel (per row)"));
     }
     const size_t smem = (size_t)b.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
-    const auto kern = sample_kernel<GUIDED, true, LOGP>;
+    const auto kern = sample_kernel<GUIDED, true, LOGP, TRUNC>;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2150,6 +2372,14 @@ int rq_launch_sample_logp(const SampleArgs& a, hipStream_t s) {
     if (a.row_temperature) return a.logits_u ? launch_sample_per_row<true, true>(a, s) : launch_sample_per_row<false, true>(a, s);
     return a.logits_u ? launch_sample<true, true>(a, s) : launch_sample<false, true>(a, s);
 }
+#elif defined(RQ_SAMPLE_TRUNC_TU)
+// a filter of min-p / typical sampling on, or per-row tables of them given: the TRUNC instantiation of whichever of the four forms the
+// arguments ask for (include/rqamd.h: rqamd_sample_logits_trunc, rqamd_rqt_sample_trunc)
+int rq_launch_sample_trunc(const SampleArgs& a, hipStream_t s) {
+    if (a.row_temperature) return a.logits_u ? launch_sample_per_row<true, true, true>(a, s) : launch_sample_per_row<false, true, true>(a, s);
+    if (a.row_min_p || a.row_typical_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: row_min_p / row_typical_p without row_temperature (null)");
+    return a.logits_u ? launch_sample<true, true, true>(a, s) : launch_sample<false, true, true>(a, s);
+}
 #elif defined(RQ_SAMPLE_GUIDED_TU)
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s) { return launch_sample<true>(a, s); }
 #else
@@ -2157,6 +2387,7 @@ int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s);     // rqt_samp
 int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s);    // rqt_sample_rows.hip
 int rq_launch_sample_logp(const SampleArgs& a, hipStream_t s);       // rqt_sample_logp.hip
 int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+    if (rq_sample_trunc_on(a)) return rq_launch_sample_trunc(a, s);     // (off values, no tables: everything below is as it was)
     if (a.logp_out) return rq_launch_sample_logp(a, s);
     if (a.row_temperature) return rq_launch_sample_per_row(a, s);
     return a.logits_u ? rq_launch_sample_guided(a, s) : launch_sample<false>(a, s);
@@ -2248,6 +2479,37 @@ extern "C" int rqamd_sample_logits_logp(const float* logits, const float* logits
     if (row_temperature) {
         a.temperature = 1.0f; a.top_k = 0; a.top_p = -1.0f;
         a.row_temperature = row_temperature; a.row_top_k = row_top_k; a.row_top_p = row_top_p; a.row_gscale = row_gscale; a.row_seeds = row_seeds;
+    }
+    a.logp_out = draw_logp_out;
+    return rq_launch_sample(a, (hipStream_t)stream);
+}
+
+// min-p and typical sampling without an engine (include/rqamd.h): the arguments of rqamd_sample_logits_logp, the two filters as scalars
+// and as per-row tables, probs_out and draw_logp_out each optional.  Both filters off and no tables: the call is the existing entry
+// point's, through rq_launch_sample's own choice.  The host sees the scalars alone and checks those; tables are the caller's.
+extern "C" int rqamd_sample_logits_trunc(const float* logits, const float* logits_u, int rows, int vocab, float temperature, int top_k,
+                                         float top_p, float min_p, float typical_p, float guidance_scale, const float* row_temperature,
+                                         const int* row_top_k, const float* row_top_p, const float* row_min_p, const float* row_typical_p,
+                                         const float* row_gscale, const uint64_t* row_seeds, uint64_t seed, uint64_t offset,
+                                         int64_t* samples_out, float* probs_out, float* draw_logp_out, int* row_flags, void* stream) {
+    if (!logits || rows < 0 || (!samples_out && !probs_out) || (draw_logp_out && !samples_out))
+        return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: bad argument (null logits, no output, draw_logp_out without samples_out, or rows < 0)");
+    if (row_temperature && (!row_top_k || !row_top_p)) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: row_temperature without row_top_k / row_top_p (null)");
+    if (!row_temperature && (row_top_k || row_top_p || row_min_p || row_typical_p || row_gscale || row_seeds))
+        return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: per-row arrays without row_temperature (null)");
+    if (row_gscale && !logits_u) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: row_gscale without logits_u (null)");
+    if (!(min_p - min_p == 0.f) || min_p > 1.0f) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: min_p must be finite and at most 1");
+    if (!(typical_p - typical_p == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "sample_logits_trunc: typical_p must be finite");
+    if (rows == 0) return RQAMD_OK;
+    SampleArgs a{};
+    a.logits = logits; a.rows = rows; a.V = vocab; a.temperature = temperature; a.top_k = top_k; a.top_p = top_p;
+    a.seed = seed; a.offset = offset; a.out = samples_out; a.out_stride = 1; a.probs_out = probs_out; a.D = 1; a.redo = row_flags;
+    a.logits_u = logits_u; a.gscale = logits_u ? guidance_scale : 1.0f;
+    a.min_p = min_p; a.typical_p = typical_p;
+    if (row_temperature) {
+        a.temperature = 1.0f; a.top_k = 0; a.top_p = -1.0f;
+        a.row_temperature = row_temperature; a.row_top_k = row_top_k; a.row_top_p = row_top_p; a.row_gscale = row_gscale; a.row_seeds = row_seeds;
+        a.row_min_p = row_min_p; a.row_typical_p = row_typical_p;
     }
     a.logp_out = draw_logp_out;
     return rq_launch_sample(a, (hipStream_t)stream);

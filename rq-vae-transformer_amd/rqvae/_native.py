@@ -69,6 +69,9 @@ _SIGS = {
     'rqamd_sample_logits_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
+    'rqamd_sample_logits_trunc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
+                                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_vae_create': (C.c_int, [C.POINTER(VaeConfig), C.POINTER(C.c_void_p)]),
     'rqamd_vae_destroy': (C.c_int, [C.c_void_p]),
     'rqamd_vae_set_option': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
@@ -94,6 +97,7 @@ _SIGS = {
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
                                         C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_sample_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_trunc': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -450,6 +454,35 @@ def sample_logits_logp(logits, logits_u=None, temperature=1.0, top_k=None, top_p
     return samples, draw
 
 
+def sample_logits_trunc(logits, logits_u=None, temperature=1.0, top_k=None, top_p=None, min_p=None, typical_p=None, guidance_scale=1.0,
+                        row_temperature=None, row_top_k=None, row_top_p=None, row_min_p=None, row_typical_p=None, row_gscale=None,
+                        row_seeds=None, seed=0, offset=0, want_probs=False, want_logp=False, want_flags=True):
+    """rqamd_sample_logits_trunc: sample_logits_logp with min-p and locally typical sampling after top-p (min_p / typical_p None: off),
+    as scalars or -- with row_temperature -- as the device tensors row_min_p / row_typical_p (rows,) float32, each or None.
+    -> (samples (rows,) int64, probs (rows, vocab) fp32 or None, draw (rows,) fp32 or None)"""
+    rows, vocab = logits.shape
+    if logits_u is not None and tuple(logits_u.shape) != (rows, vocab):
+        raise ValueError(f'sample_logits_trunc: logits_u of shape {tuple(logits_u.shape)}; expected {(rows, vocab)}')
+    for name, t, dt in (('row_temperature', row_temperature, torch.float32), ('row_top_k', row_top_k, torch.int32),
+                        ('row_top_p', row_top_p, torch.float32), ('row_min_p', row_min_p, torch.float32),
+                        ('row_typical_p', row_typical_p, torch.float32), ('row_gscale', row_gscale, torch.float32),
+                        ('row_seeds', row_seeds, torch.int64)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (rows,) or t.dtype != dt or t.device != logits.device):
+            raise ValueError(f'sample_logits_trunc: {name} must be a ({rows},) {dt} tensor on {logits.device}')
+    samples = torch.empty((rows,), dtype=torch.int64, device=logits.device)
+    probs = torch.empty((rows, vocab), dtype=torch.float32, device=logits.device) if want_probs else None
+    draw = torch.empty((rows,), dtype=torch.float32, device=logits.device) if want_logp else None
+    flags = torch.empty((max(rows, 1),), dtype=torch.int32, device=logits.device) if want_flags else None
+    with on_device_of(logits):
+        check(lib().rqamd_sample_logits_trunc(ptr(logits, torch.float32), ptr(logits_u, torch.float32), rows, vocab, float(temperature),
+                                              0 if top_k is None else int(top_k), -1.0 if top_p is None else float(top_p),
+                                              0.0 if min_p is None else float(min_p), -1.0 if typical_p is None else float(typical_p),
+                                              float(guidance_scale), ptr(row_temperature), ptr(row_top_k), ptr(row_top_p), ptr(row_min_p),
+                                              ptr(row_typical_p), ptr(row_gscale), ptr(row_seeds), int(seed) & (2 ** 64 - 1),
+                                              int(offset) & (2 ** 64 - 1), ptr(samples), ptr(probs), ptr(draw), ptr(flags), stream_of(logits)))
+    return samples, probs, draw
+
+
 def guide_logits(c, u, scale):
     """rqamd_guide_logits: classifier-free guidance on raw logits, g = c + (scale - 1) (c - u) with -inf of `c` kept (the device function
     the guided samplers apply inside the engine).  c, u (rows, vocab) fp32, contiguous, same shape -> g (rows, vocab) fp32."""
@@ -752,9 +785,24 @@ class RqtEngine(_Engine):
                     raise ValueError(f'codebook of shape {tuple(cb.shape)}; expected (>= {c.vocab_sizes[d]}, {c.input_embed_dim})')
         self._on_my_device(codes, cond, *codebooks[:c.D])
 
+    def arm_trunc(self, min_p, typical_p, per_image=False):
+        """rqamd_rqt_sample_trunc for the NEXT sample / sample_masked / sample_guided / sample_rows call of this object: min-p and
+        locally typical sampling, host sequences of D floats (per_image: B * D, image-major, in front of sample_rows only), each or
+        None = off.  (A method rather than an argument of the four: their argument lists stay as they are.)"""
+        self._trunc = (min_p, typical_p, per_image)
+
     def _sample_call(self, partial, call, want_logp, guided=False):
         """one sampling call; want_logp: armed through rqamd_rqt_sample_logp first (inside the same attempt: a failed call consumes the
-        arming) -> (draw, model, model_uncond or None), (B,H,W,D) fp32 each, else None"""
+        arming) -> (draw, model, model_uncond or None), (B,H,W,D) fp32 each, else None.  An arm_trunc() before the call is passed on
+        to rqamd_rqt_sample_trunc the same way, and consumed"""
+        trunc, self._trunc = getattr(self, '_trunc', None), None
+        if trunc is not None and (trunc[0] is not None or trunc[1] is not None):
+            arrs = [None if v is None else (C.c_float * len(v))(*[float(x) for x in v]) for v in trunc[:2]]
+            inner = call
+
+            def call():
+                rc = self._L.rqamd_rqt_sample_trunc(self._h, arrs[0], arrs[1], int(bool(trunc[2])))
+                return rc if rc != 0 else inner()
         if not want_logp:
             self._run(call)
             return None

@@ -13,6 +13,7 @@ are never ignored silently: ``cached=False`` runs a real uncached loop (every st
 cross-check of its cache, transformers.py:352-356); ``is_tqdm`` / ``desc`` have nothing to report on (the
 whole loop is one asynchronous C call) and ``fast`` is unused by the reference itself."""
 import contextlib
+import functools
 import math
 import os
 from collections import OrderedDict, namedtuple
@@ -45,6 +46,19 @@ def _attr(d):
 # it was drawn from (after guidance, temperature, top-k, top-p, renormalisation), +0.0 for kept codes; model: log_softmax of the raw
 # conditional logits at the code, NaN where the head did not run; model_uncond: the same under `uncond` (None when unguided)
 SampleLogProbs = namedtuple('SampleLogProbs', ['draw', 'model', 'model_uncond'])
+
+
+def _truncation_keywords(fn):
+    """sample() / sample_guided() also take ``min_p=`` / ``typical_p=`` as keywords: the call then runs inside ``self.truncation(...)``.
+    (A wrapper, so that the argument lists of the two methods stay the reference's plus keep_mask / uncond / guidance_scale, as for
+    seeds() and return_log_probs(); inspect.signature shows the method underneath.)"""
+    @functools.wraps(fn)
+    def with_truncation(self, *args, min_p=None, typical_p=None, **kwargs):
+        if min_p is None and typical_p is None:
+            return fn(self, *args, **kwargs)
+        with self.truncation(min_p=min_p, typical_p=typical_p):
+            return fn(self, *args, **kwargs)
+    return with_truncation
 
 
 class RQTransformer(Stage2Model):
@@ -117,6 +131,7 @@ class RQTransformer(Stage2Model):
         self.prefix_mode = os.environ.get('RQAMD_PREFIX', 'stepped')
         self._return_log_probs = False                   # inside `with self.return_log_probs()`: sample() also returns SampleLogProbs
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
+        self._truncation = (None, None)                  # (min_p, typical_p) of the sample() calls inside `with self.truncation(...)`
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -373,6 +388,7 @@ class RQTransformer(Stage2Model):
             raise ValueError('soft_target_loss(z_e=...) needs model_aux, the RQVAE whose quantiser produced the codes')
         return model_aux.quantizer
 
+    @_truncation_keywords
     @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, keep_mask=None):
@@ -391,14 +407,17 @@ class RQTransformer(Stage2Model):
         of the plain call (see return_log_probs()).
         ``self.prefix_mode = 'one_pass'``: the given leading positions (before `start_loc`, or a leading run kept in every image) fill
         the KV cache in one pass instead of one step each (see __init__); the codes then differ from the stepped mode's wherever a draw
-        was close -- GEMM tiles differ, filters and Philox counters are the same."""
+        was close -- GEMM tiles differ, filters and Philox counters are the same.
+        ``min_p=`` / ``typical_p=`` (not in the reference; keywords, or ``with self.truncation(min_p=..., typical_p=...)`` around the
+        call: see truncation()): min-p and locally typical sampling after top-p."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
         want = self._want_log_probs(cached)
-        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p)
+        trunc, force_rows = self._trunc_args(partial_sample.shape[0], *self._truncation)
+        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, force=force_rows)
         if rows is not None:
-            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, want_logp=want)
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, want_logp=want, trunc=trunc)
         top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
@@ -417,14 +436,26 @@ class RQTransformer(Stage2Model):
             return self._sample_torch_multinomial(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, keep, active)
         seed, offset = self._draw_rng(device, H * W * D)
         if not cached:
-            return self._sample_uncached(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active)
+            return self._sample_uncached(eng, xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active, trunc=trunc)
+        tr = self._trunc_engine(trunc)
+
+        def armed(call):                                 # (the arming and the call on the same stream attempt)
+            def run():
+                if not tr:
+                    return call()
+                eng.arm_trunc(*tr)
+                try:
+                    return call()
+                finally:
+                    eng.arm_trunc(None, None)        # (a call refused before it reached the library leaves nothing armed)
+            return run
         if keep is not None:
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
-            return self._with_log_probs(want, self._on_side_stream(device, lambda: eng.sample_masked(
-                xs, keep8, pos_active, c, cbs, temperature, top_k_list, top_p_list, seed, offset, self.use_graph, **want)))
-        out = self._on_side_stream(device, lambda: eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list,
-                                                              seed, offset, self.use_graph, **want))
+            return self._with_log_probs(want, self._on_side_stream(device, armed(lambda: eng.sample_masked(
+                xs, keep8, pos_active, c, cbs, temperature, top_k_list, top_p_list, seed, offset, self.use_graph, **want))))
+        out = self._on_side_stream(device, armed(lambda: eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list,
+                                                                    seed, offset, self.use_graph, **want)))
         return self._with_log_probs(want, out)
 
     @contextlib.contextmanager
@@ -459,6 +490,84 @@ class RQTransformer(Stage2Model):
             return result
         codes, lp = result
         return codes, SampleLogProbs(*lp)
+
+    @contextlib.contextmanager
+    def truncation(self, min_p=None, typical_p=None):
+        """Min-p and locally typical sampling (not in the reference) for the sample() / sample_guided() calls made inside the block --
+        or pass ``min_p=`` / ``typical_p=`` to those calls as keywords, which is the same.  Two more truncation rules, applied after
+        top-p, each to the renormalised output of the stage before it: min-p (0 < min_p <= 1) drops every code whose probability is
+        below min_p times the leader's; locally typical sampling (0 <= typical_p < 1) keeps the codes whose surprisal is closest to
+        the entropy of the distribution, in that order (ties: lowest code first), up to and including the first whose cumulative
+        mass reaches typical_p.  Each a float, a sequence of D per-depth values, or a (B,) / (B, D) tensor, which makes the call a
+        per-image call as a top_p tensor does: image b is drawn as the scalar call with b's values draws it.  None, min_p <= 0 and
+        typical_p >= 1 (or < 0) are off: the plain call, bit for bit.  Everything runs inside the engine and composes with keep_mask,
+        start_loc, seeds(), return_log_probs() (draw: the log-probability after all stages), guidance, amp and prefix_mode;
+        ``cached=False`` returns the cached call's codes; ``sampler='torch'`` raises NotImplementedError."""
+        saved, self._truncation = self._truncation, (min_p, typical_p)
+        try:
+            yield self
+        finally:
+            self._truncation = saved
+
+    def _trunc_args(self, B, min_p, typical_p):
+        """min_p / typical_p of sample() -> (None when both are off everywhere, else dict(mp=, ty=, per_image=): D values each -- or,
+        per_image, B rows of D -- with the off values 0.0 / -1.0 where a filter is off; is one of them a tensor (a per-image call)?)"""
+        D = self.block_size[2]
+
+        def per(a):
+            return torch.is_tensor(a) and a.dim() >= 1
+        per_image = per(min_p) or per(typical_p)
+        if min_p is None and typical_p is None:
+            return None, False
+        if self.sampler == 'torch':
+            raise NotImplementedError("min_p / typical_p are filters of the on-device sampler; sampler='torch' draws with torch.multinomial "
+                                      "from the reference's two filters")
+
+        def values(a, name, off):
+            if a is None:
+                v = [[off] * D]
+            elif per(a):
+                if a.dim() not in (1, 2) or a.shape[0] != B or (a.dim() == 2 and a.shape[1] != D) or not a.dtype.is_floating_point:
+                    raise ValueError(f'{name} of shape {tuple(a.shape)} / {a.dtype}; expected a floating-point ({B},) or ({B}, {D}) tensor')
+                v = (a if a.dim() == 2 else a[:, None].expand(B, D)).to(torch.float32).tolist()
+            elif isinstance(a, (int, float)) or (torch.is_tensor(a) and a.dim() == 0):
+                v = [[float(a)] * D]
+            else:
+                a = [float(x) for x in a]
+                if len(a) not in (1, D):
+                    raise ValueError(f'{name} with {len(a)} values; expected one, or one per depth ({D})')
+                v = [a * D if len(a) == 1 else a]
+            if any(not math.isfinite(x) for row in v for x in row):
+                raise ValueError(f'{name} holds a non-finite value')
+            return v
+        mp, ty = values(min_p, 'min_p', 0.0), values(typical_p, 'typical_p', -1.0)
+        if any(x > 1.0 for row in mp for x in row):
+            raise ValueError('min_p must be at most 1')
+        mp = [[x if x > 0.0 else 0.0 for x in row] for row in mp]
+        ty = [[x if 0.0 <= x < 1.0 else -1.0 for x in row] for row in ty]
+        if not any(x > 0.0 for row in mp for x in row) and not any(x >= 0.0 for row in ty for x in row):
+            return None, per_image
+        if per_image:
+            mp, ty = (m * B if len(m) == 1 else m for m in (mp, ty))
+            return dict(mp=mp, ty=ty, per_image=True), True
+        return dict(mp=mp[0], ty=ty[0], per_image=False), False
+
+    @staticmethod
+    def _trunc_engine(trunc):
+        """the arguments of RqtEngine.arm_trunc (None without a filter): D values each, or B * D image-major of a per-image call"""
+        if trunc is None:
+            return None
+        if trunc['per_image']:
+            return [x for row in trunc['mp'] for x in row], [x for row in trunc['ty'] for x in row], True
+        return trunc['mp'], trunc['ty'], False
+
+    @staticmethod
+    def _trunc_on_device(trunc, B, D, device):
+        """min_p / typical_p as the per-depth (B,) device tensors of _native.sample_logits_trunc (host loops with per-image tables)"""
+        mp = trunc['mp'] if trunc['per_image'] else [trunc['mp']] * B
+        ty = trunc['ty'] if trunc['per_image'] else [trunc['ty']] * B
+        return ([torch.tensor([r[d] for r in mp], dtype=torch.float32, device=device) for d in range(D)],
+                [torch.tensor([r[d] for r in ty], dtype=torch.float32, device=device) for d in range(D)])
 
     def _filter_lists(self, top_k, top_p):
         """top_k / top_p of sample() -> one value per depth (transformers.py:309-323)"""
@@ -505,14 +614,14 @@ class RQTransformer(Stage2Model):
         finally:
             self._image_seeds = saved
 
-    def _per_image(self, B, temperature, top_k, top_p, guidance_scale=None):
+    def _per_image(self, B, temperature, top_k, top_p, guidance_scale=None, force=False):
         """None when no argument is per image (no tensor of one or more dimensions, no seeds(): the scalar entry points, untouched), else
         the per-image tables on the host, validated: T [B], tk / tp [B][D] (clipped like _filter_lists: top_k to vocab_size[d], top_p
         to 1.0), gs [B] or None, seeds [B] or None"""
         def per(a):
             return torch.is_tensor(a) and a.dim() >= 1
-        if not (per(temperature) or per(top_k) or per(top_p) or per(guidance_scale) or self._image_seeds is not None):
-            return None
+        if not (force or per(temperature) or per(top_k) or per(top_p) or per(guidance_scale) or self._image_seeds is not None):
+            return None                                  # (force: min_p / typical_p came as tensors)
         D = self.block_size[2]
 
         def vec(a, name, default):
@@ -577,7 +686,7 @@ class RQTransformer(Stage2Model):
         return out
 
     def _sample_per_image(self, rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, guided=False, uncond=None,
-                          want_logp={}):
+                          want_logp={}, trunc=None):
         """sample() / sample_guided() with per-image parameters: rqamd_rqt_sample_rows, or the two host loops over sample_logits_rows"""
         (H, W, D) = self.block_size
         B = partial_sample.shape[0]
@@ -608,17 +717,26 @@ class RQTransformer(Stage2Model):
             if self.sampler == 'torch':
                 return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, None, None, None, keep, active, scale, rows=dev)
             seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
-            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, None, None, None, seed, offset, keep, active, scale, rows=dev)
+            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, None, None, None, seed, offset, keep, active, scale, rows=dev, trunc=trunc)
         seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
         keep8, pos_active, start = None, None, start_loc
         if keep is not None:
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
             start = (0, 0)                                                   # (the kept prefix is part of `keep`)
-        return self._with_log_probs(want_logp, self._on_side_stream(device, lambda: eng.sample_rows(
-            xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None, rows['seeds'], seed,
-            offset, self.use_graph, **want_logp)))
+        tr = self._trunc_engine(trunc)
 
+        def run():
+            if tr:
+                eng.arm_trunc(*tr)
+            try:
+                return eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None,
+                                       rows['seeds'], seed, offset, self.use_graph, **want_logp)
+            finally:
+                eng.arm_trunc(None, None)
+        return self._with_log_probs(want_logp, self._on_side_stream(device, run))
+
+    @_truncation_keywords
     @torch.no_grad()
     def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                       amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, uncond=None, guidance_scale=1.0,
@@ -632,14 +750,17 @@ class RQTransformer(Stage2Model):
         sample() over the 2B rows, the former bit for bit equal to ``cached=True``.  Per-image ``temperature`` / ``top_k`` / ``top_p``
         tensors and ``with self.seeds(...)`` as in sample(); ``guidance_scale`` as a (B,) tensor gives every image its own scale.
         Inside ``with self.return_log_probs():`` the call returns ``(codes, SampleLogProbs(draw, model, model_uncond))``, draw under the
-        guided distribution, model / model_uncond under the raw logits of the two twins."""
+        guided distribution, model / model_uncond under the raw logits of the two twins.  ``min_p`` / ``typical_p`` as in sample(),
+        applied to the guided distribution."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
         want = self._want_log_probs(cached)
-        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, guidance_scale)
+        trunc, force_rows = self._trunc_args(partial_sample.shape[0], *self._truncation)
+        rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, guidance_scale, force=force_rows)
         if rows is not None:
-            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, True, uncond, want_logp=want)
+            return self._sample_per_image(rows, partial_sample, model_aux, cond, start_loc, amp, cached, keep_mask, True, uncond, want_logp=want,
+                                          trunc=trunc)
         if not math.isfinite(float(guidance_scale)):
             raise ValueError(f'guidance_scale {guidance_scale} is not finite')
         scale = float(guidance_scale)
@@ -667,15 +788,25 @@ class RQTransformer(Stage2Model):
             if self.sampler == 'torch':
                 return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, keep, active, scale)
             seed, offset = self._draw_rng(device, H * W * D)
-            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active, scale)
+            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active, scale,
+                                         trunc=trunc)
         seed, offset = self._draw_rng(device, H * W * D)
         keep8, pos_active, start = None, None, start_loc
         if keep is not None:
             keep8 = keep.to(torch.uint8).contiguous()
             pos_active = [bool(a) for a in active.any(dim=1).tolist()]
             start = (0, 0)                                                   # (the kept prefix is part of `keep`)
-        return self._with_log_probs(want, self._on_side_stream(device, lambda: eng.sample_guided(
-            xs, keep8, pos_active, c, u, cbs, start, temperature, scale, top_k_list, top_p_list, seed, offset, self.use_graph, **want)))
+        tr = self._trunc_engine(trunc)
+
+        def run():
+            if tr:
+                eng.arm_trunc(*tr)
+            try:
+                return eng.sample_guided(xs, keep8, pos_active, c, u, cbs, start, temperature, scale, top_k_list, top_p_list, seed, offset,
+                                         self.use_graph, **want)
+            finally:
+                eng.arm_trunc(None, None)
+        return self._with_log_probs(want, self._on_side_stream(device, run))
 
     def _keep_flags(self, keep_mask, xs, start_loc):
         """keep_mask of sample() -> (keep (B,H,W,D) bool on the device of `xs`, active (H*W, D) bool on the host: some row draws that
@@ -710,7 +841,7 @@ class RQTransformer(Stage2Model):
         return keep, host[:-1].view(H * W, D)
 
     def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None,
-                         guidance_scale=None, rows=None):
+                         guidance_scale=None, rows=None, trunc=None):
         """``cached=False`` (transformers.py:352-356): nothing is carried from one step to the next -- every step recomputes the
         logits of the whole code map from the codes drawn so far (one teacher-forced pass of the engine per step, 256 per
         batch, as slow as the reference's own uncached loop) and samples position (h, w, d) from them with the draw the
@@ -722,12 +853,15 @@ class RQTransformer(Stage2Model):
         from guide_logits of the two halves -- Philox row b, as the engine's guided sampler -- and writes the code to both halves;
         `keep` has B rows and the first B rows are returned.
         ``rows`` (per-image parameters, _rows_on_device): the draw is sample_logits_rows with the tables of the rows -- and
-        guidance_scale a list, one scale per image -- in place of the scalars; with seeds, key seeds[b] and counter pos * D + d."""
+        guidance_scale a list, one scale per image -- in place of the scalars; with seeds, key seeds[b] and counter pos * D + d.
+        ``trunc`` (_trunc_args): min-p / typical sampling, the draw by sample_logits_trunc with the depth's values (or tables)."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
         xs = xs.clone()
         n = xs.shape[0] // 2 if guidance_scale is not None else xs.shape[0]
+        if trunc is not None and rows is not None:
+            mp_dev, ty_dev = self._trunc_on_device(trunc, n, D, xs.device)
         for pos in range(start, H * W):
             h, w = divmod(pos, W)
             for d in range(D):
@@ -740,7 +874,14 @@ class RQTransformer(Stage2Model):
                     logits = self._guide_rows(logits[:n], logits[n:], guidance_scale)
                 elif guidance_scale is not None:
                     logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
-                if rows is not None:
+                if trunc is not None and rows is not None:
+                    idx = _native.sample_logits_trunc(logits, row_temperature=rows['T_dev'], row_top_k=rows['tk_dev'][d], row_top_p=rows['tp_dev'][d],
+                                                      row_min_p=mp_dev[d], row_typical_p=ty_dev[d], row_seeds=rows['seeds_dev'], seed=seed,
+                                                      offset=offset + pos * D + d)[0]
+                elif trunc is not None:
+                    idx = _native.sample_logits_trunc(logits, temperature=temperature, top_k=top_k_list[d], top_p=top_p_list[d],
+                                                      min_p=trunc['mp'][d], typical_p=trunc['ty'][d], seed=seed, offset=offset + pos * D + d)[0]
+                elif rows is not None:
                     idx, _ = _native.sample_logits_rows(logits, rows['T_dev'], rows['tk_dev'][d], rows['tp_dev'][d], seeds=rows['seeds_dev'],
                                                         seed=seed, offset=offset + pos * D + d)
                 else:
