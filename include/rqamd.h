@@ -332,6 +332,26 @@ int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* model_logp_
  * sets of their own (scalar values are part of their key, per-image values live in tables of the handle and a new set of values
  * replays the same graphs): alternating armed and unarmed calls recaptures nothing. */
 int rqamd_rqt_sample_trunc(rqamd_rqt* h, const float* min_p, const float* typical_p, int per_image);
+/* Sampling schedules over positions and depths (not in the reference); additive, ABI v7.  Arms the NEXT rqamd_rqt_sample, _masked,
+ * _guided or _rows call on the handle; that call consumes the arming whether it succeeds or fails, and reads the arrays: HOST arrays
+ * of H * W * D values in raster order, depth last (per_image = 0: one schedule for every image), or of batch * H * W * D values,
+ * image-major (per_image = 1; valid in front of any of the four).  A NULL pointer: that parameter comes from the armed call's own
+ * arguments (a number, per-depth values, per-image values, or an arming of rqamd_rqt_sample_trunc), broadcast over the positions; all
+ * NULL disarms.  Code (b, p, d) is then drawn, bit for bit, as rqamd_sample_logits_rows -- rqamd_sample_logits_trunc where a min-p /
+ * typical value is on there -- draws row b from the same logits (the guided mix with the scale at (b, p, d) included) with the values
+ * at (b, p, d); Philox key, row field and counter offset + p * D + d are those of the unarmed call (per-image seeds: of
+ * rqamd_rqt_sample_rows).  So a schedule that is constant over the positions returns the per-image call's codes, and the scalar
+ * call's.  top_k <= 0 or >= vocab, top_p < 0 or >= 1, min_p <= 0 and typical_p < 0 or >= 1 are off, as in the per-row arrays.
+ * The armed call checks the values on the host before anything is enqueued: a temperature that is not finite and > 0, a non-finite
+ * guidance scale, min_p or typical_p, a min_p above 1, or a guidance schedule in front of an unguided call make it
+ * RQAMD_ERR_INVALID, and nothing is written.  Kept codes, start_h / start_w, pos_active_host, "prefix.one_pass" and the two other
+ * armings behave as without a schedule (draw: the log-probability after all stages, with the values of the position).
+ * The values live in device tables of the handle -- H * W * D entries each for a shared schedule, batch * H * W * D (allocated at
+ * the first such call and kept) when the schedule or any argument is per image -- which the sampler kernels index with the position
+ * they read from the device.  Scheduled calls always take the per-row launch sequence and replay graph sets of their own, whose keys
+ * hold no value: another schedule replays the same graphs, and scheduled, per-image and scalar calls never recapture each other's. */
+int rqamd_rqt_sample_schedule(rqamd_rqt* h, const float* temperature, const int* top_k, const float* top_p,
+                              const float* guidance_scale, const float* min_p, const float* typical_p, int per_image);
 /* *captures = the number of position graphs this handle has captured so far (every form of sampling); a call that replays only
  * leaves it unchanged. */
 int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures);

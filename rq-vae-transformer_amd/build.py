@@ -9,18 +9,18 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'librqamd.so')
-SOURCES = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip',
+SOURCES = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip',
            'engine_vae.hip']
 # sources that #include another .hip (the sampler section of rqt_kernels.hip, instantiated once more): rebuilt when that file changes
 INCLUDES = {'rqt_sample_guided.hip': ['rqt_kernels.hip'], 'rqt_sample_rows.hip': ['rqt_kernels.hip'], 'rqt_sample_logp.hip': ['rqt_kernels.hip'],
-            'rqt_sample_trunc.hip': ['rqt_kernels.hip']}
+            'rqt_sample_trunc.hip': ['rqt_kernels.hip'], 'rqt_sample_sched.hip': ['rqt_kernels.hip']}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-I', CSRC]
 # librqamd_f16.so: the two engines once more with IEEE fp16 as the 16-bit storage type (csrc/rq_hip.h, -DRQ_F16=1) -- what
 # RQTransformer.sample(amp=True) / forward(amp=True) run on, as the reference's fp16 autocast does (transformers.py:21,206), and what the
 # opt-in RQAMD_VAE=fp16 RQ-VAE engine runs on.  Same C ABI (the rqamd_rqt_* / rqamd_vae_* entry points, rqamd_abi_version,
 # rqamd_last_error); the quantiser (fp32 arithmetic, the same code in both) is in it for rqamd_rqt_soft_loss, which forms soft targets from features.
 OUT_F16 = os.path.join(HERE, 'librqamd_f16.so')
-SOURCES_F16 = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip', 'engine_vae.hip']
+SOURCES_F16 = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip', 'engine_vae.hip']
 
 
 def _newer(a, b):

@@ -97,6 +97,19 @@ struct rqamd_rqt {
     struct LogpArm { float *draw, *model, *model_u; bool on() const { return draw || model || model_u; } } arm = {};   // outputs of the next sampling call
     // the arming of rqamd_rqt_sample_trunc: HOST arrays, read by the next sampling call (D entries each, or batch * D image-major)
     struct TruncArm { const float *min_p, *typical_p; int per_image; bool on() const { return min_p || typical_p; } } tarm = {};
+    // sampling schedules (rqamd_rqt_sample_schedule): the arming -- HOST arrays of HW * D values (per_image: batch * HW * D, image-major),
+    // read by the next sampling call -- and the device tables the scheduled sampler launches read at [row * row_stride + pos * D + d].
+    // `sch_shared` ([HW][D] each, row_stride 0) comes from the slab; `sch_image` ([images][HW][D] each) is memory of its own, allocated by
+    // the first call that needs it, outside any capture, and kept -- it grows with the batch, which drops the graphs that hold its addresses.
+    // Every table a call's launches read is filled before the position loop, the captured graphs hold addresses only
+    struct SchedArm {
+        const float* temperature; const int* top_k; const float *top_p, *gscale, *min_p, *typical_p; int per_image;
+        bool on() const { return temperature || top_k || top_p || gscale || min_p || typical_p; }
+    } sarm = {};
+    struct SchedTables { float* T; int* tk; float *tp, *gs, *mp, *typ; } sch_shared = {}, sch_image = {};
+    DevBuf sch_image_buf;
+    size_t sch_image_rows = 0;      // images the tables of sch_image hold
+    std::vector<char> sch_host;     // host staging of the tables, like row_host
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -120,8 +133,13 @@ struct rqamd_rqt {
     // Calls with min-p / typical sampling in effect (rqamd_rqt_sample_trunc: other sampler kernels at the depths with a filter on) are
     // all twelve once more, gkey[12] .. gkey[23] and sets [24] .. [47].  Their scalar values are in the key next to tk / tp (mp, typ:
     // zero in every other family's key); per-image values are in h->row_mp / h->row_typ and in no key.
+    // Scheduled calls (rqamd_rqt_sample_schedule: the scheduled per-row sampler kernels) are 32 more families, gkey[24] .. gkey[55] and
+    // sets [48] .. [111] (step_family: filters / armed / seeded / per-image tables / guided, a bit each).  Every value is in a table, so
+    // like the per-row keys theirs hold rows, codebooks, stream and the guided flag alone: other values replay the same graphs, and
+    // scalar, per-row and scheduled families never invalidate each other.
     static constexpr int NGRAPH = 33;
-    static constexpr int NFAM = 24;
+    static constexpr int NFAM_SCHED0 = 24;         // first scheduled family
+    static constexpr int NFAM = 56;
     hipGraphExec_t gexec[2 * NFAM][NGRAPH] = {};
     struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; } gkey[NFAM];
     bool gkey_set[NFAM] = {}, gstale[NFAM] = {};
@@ -441,7 +459,8 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + al(brows * V * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
                    + al(rows * 4 * E * 2) + al(brows * h->Din * 2) + al(brows * h->HW * h->D * 8) + al(brows * h->cond_len * 8) + al(64) + al(64) + al(brows * 4)
                    + al(brows * h->HW * h->D)
-                   + 2 * al(brows * 4) + 4 * al(brows * h->D * 4) + al(brows * 8) + 2 * al(brows * h->HW * h->D * 4);
+                   + 2 * al(brows * 4) + 4 * al(brows * h->D * 4) + al(brows * 8) + 2 * al(brows * h->HW * h->D * 4)
+                   + 6 * al((size_t)h->HW * h->D * 4);
     RQ_TRY(h->ws.reserve(total));
     char* p = (char*)h->ws.p;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
@@ -459,6 +478,11 @@ static int ensure_batch(rqamd_rqt* h, int B) {
     h->row_seed = (uint64_t*)take(brows * 8);
     h->row_mp = (float*)take(brows * h->D * 4); h->row_typ = (float*)take(brows * h->D * 4);
     h->logp_draw = (float*)take(brows * h->HW * h->D * 4); h->logp_model = (float*)take(brows * h->HW * h->D * 4);
+    {   // one schedule shared by all images: six [HW][D] tables, whatever the batch
+        const size_t sb = (size_t)h->HW * h->D * 4;
+        rqamd_rqt::SchedTables& t = h->sch_shared;
+        t.T = (float*)take(sb); t.tk = (int*)take(sb); t.tp = (float*)take(sb); t.gs = (float*)take(sb); t.mp = (float*)take(sb); t.typ = (float*)take(sb);
+    }
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
     const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
     // (8-bit keys: half the bytes for K plus one fp32 scale per (row, head, position))
@@ -617,6 +641,8 @@ struct StepCtx {
     bool trunc;            // min-p / typical sampling in effect (rqamd_rqt_sample_trunc): scalar calls read min_p[d] / typical_p[d] (host arrays of
     const float* min_p;    //   D values, off values where a filter is not given: a depth with both off launches what it launches unarmed); per-row
     const float* typical_p; //  calls read h->row_mp / h->row_typ at every depth
+    bool sched;            // scheduled call (rqamd_rqt_sample_schedule): the scheduled per-row samplers read EVERY parameter at (row, position, depth) from
+    bool sched_per_image;  //   h->sch_image (a schedule per image) or h->sch_shared (one for all rows); trunc: the min-p / typical tables are read too
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -709,14 +735,22 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
         s.redo = h->smp_redo; s.rng = h->rng; s.pos = h->st; s.d = d; s.D = h->D; s.out = h->xs; s.out_stride = (long)h->HW * h->D;
         s.keep = c.keep; s.keep_stride = s.out_stride;
         if (c.guided) { s.rows = c.Bs; s.logits_u = h->logits + (long)c.Bs * h->V; s.gscale = c.gscale; s.out_mirror = (long)c.Bs * s.out_stride; }
-        if (c.per_row) {       // rows 0 .. Bs-1 of the tables, for both twins of a guided pair
+        if (c.sched) {         // every value from the tables of the schedule, at (row, *st, d); the scalars are unused
+            const rqamd_rqt::SchedTables& t = c.sched_per_image ? h->sch_image : h->sch_shared;
+            s.temperature = 1.f; s.top_k = 0; s.top_p = -1.f;
+            s.sched = 1; s.row_stride = c.sched_per_image ? (long)h->HW * h->D : 0;
+            s.row_temperature = t.T; s.row_top_k = t.tk; s.row_top_p = t.tp;
+            s.row_gscale = c.guided ? t.gs : nullptr;
+            if (c.row_seeds) { s.row_seeds = h->row_seed; s.rng = nullptr; }
+            if (c.trunc) { s.row_min_p = t.mp; s.row_typical_p = t.typ; }
+        } else if (c.per_row) {       // rows 0 .. Bs-1 of the tables, for both twins of a guided pair
             s.temperature = 1.f; s.top_k = 0; s.top_p = -1.f;
             s.row_temperature = h->row_T; s.row_top_k = h->row_tk; s.row_top_p = h->row_tp;
             s.row_gscale = c.guided ? h->row_gs : nullptr;
             if (c.row_seeds) { s.row_seeds = h->row_seed; s.rng = nullptr; }      // key row_seed[b], counter 0 + slot (s.offset is 0)
         }
         if (c.logp) s.logp_out = h->logp_draw;
-        if (c.trunc) {
+        if (c.trunc && !c.sched) {
             if (c.per_row) { s.row_min_p = h->row_mp; s.row_typical_p = h->row_typ; }
             else { s.min_p = c.min_p[d]; s.typical_p = c.typical_p[d]; }
         }
@@ -735,6 +769,13 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
                                 hipMemcpyDeviceToDevice, st));
     }
     return RQAMD_OK;
+}
+
+// the graph family of a sampling call (rqamd_rqt::gkey): scalar and per-row calls 0 .. 23, scheduled calls from NFAM_SCHED0 on
+static int step_family(const StepCtx& c) {
+    if (c.sched)
+        return rqamd_rqt::NFAM_SCHED0 + (c.trunc ? 16 : 0) + (c.logp ? 8 : 0) + (c.row_seeds ? 4 : 0) + (c.sched_per_image ? 2 : 0) + (c.guided ? 1 : 0);
+    return (c.trunc ? 12 : 0) + (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
 }
 
 // everything that happens at one spatial position (position read from h->st[0] on the device)
@@ -825,7 +866,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         RQ_LAUNCH(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->logp_model, __builtin_nanf(""), n);
         RQ_TRY(rq_check_launch("fill_f32_kernel"));
     }
-    const int fam = (c.trunc ? 12 : 0) + (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
+    const int fam = step_family(c);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = n0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
@@ -893,7 +934,7 @@ static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
 }
 struct ArmGuard {          // an entry point that returns before sample_impl still consumes the armings
     rqamd_rqt* h;
-    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; } }
+    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; } }
 };
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
@@ -907,6 +948,8 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     const rqamd_rqt::LogpArm arm = take_arm(h);        // (consumed here at the latest: the entry points take it before their own checks)
     const rqamd_rqt::TruncArm tarm = h->tarm;
     h->tarm = {};
+    const rqamd_rqt::SchedArm sarm = h->sarm;
+    h->sarm = {};
     if (arm.model_u && !guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: model_logp_uncond_out armed for an unguided call");
     // min-p / typical values of the call: tr_mp / tr_typ hold D values (scalar calls) or batch * D (per-row calls: a D-entry arming is
     // repeated for every image), off values where a filter is not given.  Scalar calls whose every value is off are unarmed calls.
@@ -927,6 +970,20 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             trunc = trunc || tr_mp[i] > 0.f || tr_typ[i] >= 0.f;
         }
         if (rp) trunc = true;          // per-row: the tables are read on the device, whatever they hold
+    }
+    // a schedule armed by rqamd_rqt_sample_schedule: its values are checked here, before anything is enqueued or written
+    const size_t sn = (size_t)h->HW * h->D;
+    if (sarm.on()) {
+        if (sarm.gscale && !guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: a guidance schedule armed in front of an unguided call");
+        const size_t n = (sarm.per_image ? (size_t)batch : 1) * sn;
+        for (size_t i = 0; i < n; ++i) {
+            if (sarm.temperature && (!(sarm.temperature[i] > 0.f) || !(sarm.temperature[i] - sarm.temperature[i] == 0.f)))
+                return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: temperature[%zu] must be > 0 and finite", i);
+            if (sarm.gscale && !(sarm.gscale[i] - sarm.gscale[i] == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: guidance_scale[%zu] must be finite", i);
+            if (sarm.min_p && (!(sarm.min_p[i] - sarm.min_p[i] == 0.f) || sarm.min_p[i] > 1.0f))
+                return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: min_p[%zu] must be finite and at most 1", i);
+            if (sarm.typical_p && !(sarm.typical_p[i] - sarm.typical_p[i] == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: typical_p[%zu] must be finite", i);
+        }
     }
     const int rows = guided ? 2 * batch : batch;
     RQ_TRY(ensure_batch(h, rows));
@@ -961,17 +1018,69 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             RQ_HIP(hipMemcpyAsync(h->row_typ, hb + oY, nD * 4, hipMemcpyHostToDevice, st));
         }
     }
+    if (sarm.on()) {
+        // The tables of the scheduled call: a value for every (image, position, depth) -- or, one schedule for all images and no per-image
+        // argument anywhere, for every (position, depth) -- from the schedule where it gives the parameter, else from the call's own
+        // arguments, broadcast.  Host staging block -> device tables by asynchronous copies ahead of the position loop, as above.
+        const bool pi = sarm.per_image || rp;
+        const size_t nimg = pi ? (size_t)batch : 1, nt = nimg * sn;
+        const int D = h->D;
+        RQ_HIP(hipStreamSynchronize(st));
+        h->sch_host.resize(6 * nt * 4);
+        float* hT = (float*)h->sch_host.data();
+        int* hK = (int*)(hT + nt);
+        float *hP = (float*)(hK + nt), *hG = hP + nt, *hM = hG + nt, *hY = hM + nt;
+        bool any_trunc = false;
+        for (size_t b = 0; b < nimg; ++b) {
+            for (size_t q = 0; q < sn; ++q) {
+                const size_t i = b * sn + q, j = (sarm.per_image ? b * sn : 0) + q, d = q % D;
+                hT[i] = sarm.temperature ? sarm.temperature[j] : rp ? rp->temperature[b] : temperature;
+                hK[i] = sarm.top_k ? sarm.top_k[j] : rp ? rp->top_k[b * D + d] : top_k[d];
+                hP[i] = sarm.top_p ? sarm.top_p[j] : rp ? rp->top_p[b * D + d] : top_p[d];
+                hG[i] = !guided ? 1.f : sarm.gscale ? sarm.gscale[j] : rp ? rp->gscale[b] : gscale;
+                float m = sarm.min_p ? sarm.min_p[j] : tr_mp.empty() ? 0.f : tr_mp[(rp ? b * D : 0) + d];
+                float y = sarm.typical_p ? sarm.typical_p[j] : tr_typ.empty() ? -1.f : tr_typ[(rp ? b * D : 0) + d];
+                if (!(m > 0.f)) m = 0.f;                                   // the off values of the per-row arrays
+                if (!(y >= 0.f && y < 1.0f)) y = -1.f;
+                hM[i] = m; hY[i] = y;
+                any_trunc = any_trunc || m > 0.f || y >= 0.f;
+            }
+        }
+        trunc = any_trunc;             // a filter on somewhere: the TRUNC builds read the two tables; nowhere: the builds without the stages
+        if (pi && (size_t)batch > h->sch_image_rows) {
+            // first use, or a larger batch: outside any capture.  The graphs of the per-image scheduled families hold the old addresses
+            h->sch_image_rows = 0;
+            const size_t tb = al((size_t)batch * sn * 4);
+            RQ_TRY(h->sch_image_buf.reserve(6 * tb));
+            char* q = (char*)h->sch_image_buf.p;
+            rqamd_rqt::SchedTables& t = h->sch_image;
+            t.T = (float*)q; t.tk = (int*)(q + tb); t.tp = (float*)(q + 2 * tb); t.gs = (float*)(q + 3 * tb); t.mp = (float*)(q + 4 * tb); t.typ = (float*)(q + 5 * tb);
+            h->sch_image_rows = (size_t)batch;
+            for (int f = rqamd_rqt::NFAM_SCHED0; f < rqamd_rqt::NFAM; ++f) if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = true;
+        }
+        const rqamd_rqt::SchedTables& t = pi ? h->sch_image : h->sch_shared;
+        RQ_HIP(hipMemcpyAsync(t.T, hT, nt * 4, hipMemcpyHostToDevice, st));
+        RQ_HIP(hipMemcpyAsync(t.tk, hK, nt * 4, hipMemcpyHostToDevice, st));
+        RQ_HIP(hipMemcpyAsync(t.tp, hP, nt * 4, hipMemcpyHostToDevice, st));
+        if (guided) RQ_HIP(hipMemcpyAsync(t.gs, hG, nt * 4, hipMemcpyHostToDevice, st));
+        if (trunc) {
+            RQ_HIP(hipMemcpyAsync(t.mp, hM, nt * 4, hipMemcpyHostToDevice, st));
+            RQ_HIP(hipMemcpyAsync(t.typ, hY, nt * 4, hipMemcpyHostToDevice, st));
+        }
+        c.sched = true; c.sched_per_image = pi; c.trunc = trunc;
+        c.row_seeds = rp && rp->seeds;
+    }
     // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
     // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
     rqamd_rqt::Key k{};
     k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream;
     for (int d = 0; d < h->D; ++d) k.cb[d] = codebooks[d];
-    if (!rp) {             // (per-row calls: no parameter value is in a captured launch, so none is in the key)
+    if (!rp && !sarm.on()) {       // (per-row and scheduled calls: no parameter value is in a captured launch, so none is in the key)
         k.T = temperature; k.gs = guided ? gscale : 0.f;
         for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
         if (trunc) for (int d = 0; d < h->D; ++d) { k.mp[d] = tr_mp[d]; k.typ[d] = tr_typ[d]; }
     }
-    const int fam = (trunc ? 12 : 0) + (arm.on() ? 6 : 0) + (rp ? (rp->seeds ? 4 : 2) : 0) + (guided ? 1 : 0);
+    const int fam = step_family(c);
     if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
@@ -1091,6 +1200,17 @@ extern "C" int rqamd_rqt_sample_logp(rqamd_rqt* h, float* draw_logp_out, float* 
 extern "C" int rqamd_rqt_sample_trunc(rqamd_rqt* h, const float* min_p, const float* typical_p, int per_image) {
     if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_trunc: null handle");
     h->tarm = rqamd_rqt::TruncArm{min_p, typical_p, (min_p || typical_p) && per_image ? 1 : 0};
+    return RQAMD_OK;
+}
+
+// Arms the next rqamd_rqt_sample / _masked / _guided / _rows call on the handle with sampling schedules over positions and depths
+// (include/rqamd.h): HOST arrays of H * W * D values -- batch * H * W * D image-major with per_image = 1 -- read and checked by that
+// call, each or NULL (the parameter comes from the call's own arguments); all NULL disarms.
+extern "C" int rqamd_rqt_sample_schedule(rqamd_rqt* h, const float* temperature, const int* top_k, const float* top_p,
+                                         const float* guidance_scale, const float* min_p, const float* typical_p, int per_image) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: null handle");
+    h->sarm = rqamd_rqt::SchedArm{temperature, top_k, top_p, guidance_scale, min_p, typical_p, 0};
+    h->sarm.per_image = h->sarm.on() && per_image ? 1 : 0;
     return RQAMD_OK;
 }
 

@@ -113,7 +113,14 @@ struct SampleArgs {
     float typical_p = -1.f;         // < 0 or >= 1: off; else the prefix of the |surprisal - entropy| order that reaches this mass
     const float* row_min_p = nullptr;       // [rows * D], or null
     const float* row_typical_p = nullptr;   // [rows * D], or null
+    // sampling schedules over positions and depths (rqamd_rqt_sample_schedule): sched != 0 selects the SCHED instantiations of the
+    // per-row kernels (rqt_sample_sched.hip), which read EVERY table above -- row_temperature and row_gscale included, row_seeds not --
+    // at [row * row_stride + *pos * D + d]: row_stride = HW * D for a schedule per image, 0 for one shared by all rows.  `pos` is
+    // required.  Row r at (pos, d) is drawn exactly as the per-row kernels draw it with the values the tables hold there.
+    int sched = 0;
+    long row_stride = 0;
 };
+int rq_launch_sample_sched(const SampleArgs& a, hipStream_t s);     // rqt_sample_sched.hip
 // is a filter of the TRUNC instantiations in effect (scalars), or could one be (tables)?
 static inline bool rq_sample_trunc_on(const SampleArgs& a) {
     return a.row_min_p || a.row_typical_p || a.min_p > 0.f || (a.typical_p >= 0.f && a.typical_p < 1.0f);

@@ -20,7 +20,9 @@ static __device__ __forceinline__ float rq_u01(uint32_t r) { return fmaf((float)
 // instantiations (ROWS = true, unguided and guided), for the same reason, and rqt_sample_logp.hip with RQ_SAMPLE_LOGP_TU for the
 // instantiations that also report the log-probability of the draw (LOGP = true, all four of the above), and rqt_sample_trunc.hip with
 // RQ_SAMPLE_TRUNC_TU for the ones with the min-p and typical stages (TRUNC = true, all four once more).
-#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU)
+// rqt_sample_sched.hip (RQ_SAMPLE_SCHED_TU): the scheduled form of every per-row instantiation (SCHED = true: the tables are indexed by
+// position and depth as well).
+#if defined(RQ_SAMPLE_GUIDED_TU) || defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU) || defined(RQ_SAMPLE_SCHED_TU)
 #define RQ_SAMPLE_ONLY_TU 1
 #endif
 #ifndef RQ_SAMPLE_ONLY_TU
@@ -1493,6 +1495,38 @@ static __device__ __forceinline__ void sample_row_params(SampleArgs& p, int row)
         if (p.row_typical_p) p.typical_p = p.row_typical_p[(long)row * p.D + p.d];
     }
 }
+// SCHED (rqt_sample_sched.hip, rqamd_rqt_sample_schedule): every table -- row_temperature and row_gscale too -- holds a value per
+// (position, depth) and is read at [row * row_stride + *pos * D + d]; row_stride = 0: one schedule shared by all rows.  *pos is the device
+// counter the kernels read for the output slot and the Philox counter, so the index is uniform over the workgroup like the per-row one.
+// The two functions above with that index, and functions of their own: the per-row kernels' instruction streams stay as they were.
+static __device__ __forceinline__ long sample_sched_index(const SampleArgs& p, int row) {
+    return (long)row * p.row_stride + (long)((*p.pos) * p.D + p.d);
+}
+template <bool TRUNC = false>
+static __device__ __forceinline__ int sample_sched_class(const SampleArgs& p, int row) {
+    const long i = sample_sched_index(p, row);
+    const int k = p.row_top_k[i];
+    const float tp = p.row_top_p[i];
+    const bool k_on = k > 0 && k < p.V;
+    bool t_on = false;
+    if (TRUNC) t_on = trunc_min_p_on(p.row_min_p ? p.row_min_p[i] : p.min_p) || trunc_typical_on(p.row_typical_p ? p.row_typical_p[i] : p.typical_p);
+    if (!k_on && (tp < 0.f || tp >= 1.0f) && !t_on && !p.probs_out && p.out) return SMP_ROW_GUMBEL;
+    if (k_on && p.V <= SMP_T * SMP_VPT && p.V % 4 == 0 && p.redo) return SMP_ROW_TOPK;
+    return SMP_ROW_GENERAL;
+}
+template <bool TRUNC = false>
+static __device__ __forceinline__ void sample_sched_params(SampleArgs& p, int row) {
+    const long i = sample_sched_index(p, row);
+    p.temperature = p.row_temperature[i];
+    p.top_k = p.row_top_k[i];
+    p.top_p = p.row_top_p[i];
+    if (p.row_gscale) p.gscale = p.row_gscale[i];
+    if (p.row_seeds) { p.rng = nullptr; p.seed = p.row_seeds[row]; }      // (one seed per row, as in the per-row form)
+    if (TRUNC) {
+        if (p.row_min_p) p.min_p = p.row_min_p[i];
+        if (p.row_typical_p) p.typical_p = p.row_typical_p[i];
+    }
+}
 
 // The three samplers are templates on GUIDED.  <false>: the unguided kernels, whose instruction stream the parameter leaves as it was.
 // <true>: the row of p.logits_u is loaded next to the row of p.logits, the same way, and the two are mixed through guide_logit();
@@ -1628,7 +1662,7 @@ static __device__ __forceinline__ void trunc_lds(const SampleArgs& p, float* sx,
 // LOGP (rqt_sample_logp.hip): the log of the probability the drawn code had in the distribution the draw was made from -- after
 // guidance, temperature, top-k, top-p and renormalisation -- goes to p.logp_out, addressed like p.out (no mirror).  <.., false>: as before.
 // TRUNC kernels are built with LOGP = true alone and write where p.logp_out is given.
-template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false, bool SCHED = false>
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     RQ_DYN_SMEM(smem);
     float* sx = (float*)smem;                  // [V] logits -> probabilities
@@ -1640,9 +1674,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs p) {
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (ROWS) {                                // the general rows, and the register kernel's rows that it handed back
-        const int cls = sample_row_class<TRUNC>(p, row);
+        const int cls = SCHED ? sample_sched_class<TRUNC>(p, row) : sample_row_class<TRUNC>(p, row);
         if (cls == SMP_ROW_GUMBEL || (cls == SMP_ROW_TOPK && !p.redo[row])) return;
-        sample_row_params<TRUNC>(p, row);
+        if (SCHED) sample_sched_params<TRUNC>(p, row);
+        else sample_row_params<TRUNC>(p, row);
     }
     if (!ROWS && p.redo && !p.redo[row]) return;        // second pass after sample_topk_kernel: only the rows it handed back
     const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
@@ -2067,14 +2102,15 @@ static __device__ __forceinline__ void sample_tail(const SampleArgs& p, float (&
     }
 }
 
-template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false, bool SCHED = false>
 __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
     __shared__ SmpShared sh;
     const int tid = threadIdx.x, lane = tid & 63, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given (redo[row] is neither written nor read)
     if (ROWS) {                                // rows of another class leave redo[row] alone: the general kernel reads it for this class only
-        if (sample_row_class<TRUNC>(p, row) != SMP_ROW_TOPK) return;
-        sample_row_params<TRUNC>(p, row);
+        if ((SCHED ? sample_sched_class<TRUNC>(p, row) : sample_row_class<TRUNC>(p, row)) != SMP_ROW_TOPK) return;
+        if (SCHED) sample_sched_params<TRUNC>(p, row);
+        else sample_row_params<TRUNC>(p, row);
     }
     const float* lg = p.logits + (long)row * V;
     const int V4 = V >> 2;
@@ -2203,7 +2239,7 @@ __global__ __launch_bounds__(SMP_T) void sample_topk_kernel(SampleArgs p) {
 // LOGP: the streaming pass has no normalisation, so each thread also keeps a running (max, sum of exp) over its scrubbed, scaled values
 // -- the `take` of log_prob_kernel, one rescale per new maximum -- and the winner's own value; the four wavefronts combine them and
 // thread 0 writes x_best - M - logf(S).  expf / logf here, not the one-instruction forms: the result is not rounded to 16 bits afterwards.
-template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false>      // TRUNC: the class rule alone (a filtered row never streams)
+template <bool GUIDED, bool ROWS = false, bool LOGP = false, bool TRUNC = false, bool SCHED = false>      // TRUNC: the class rule alone (a filtered row never streams)
 __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     __shared__ float red[4];
     __shared__ int redi[4];
@@ -2211,8 +2247,9 @@ __global__ __launch_bounds__(256) void sample_gumbel_kernel(SampleArgs p) {
     const int tid = threadIdx.x, V = p.V, row = blockIdx.x;
     if (sample_kept(p, row)) return;           // masked sampling: the code is given
     if (ROWS) {
-        if (sample_row_class<TRUNC>(p, row) != SMP_ROW_GUMBEL) return;
-        sample_row_params<TRUNC>(p, row);
+        if ((SCHED ? sample_sched_class<TRUNC>(p, row) : sample_row_class<TRUNC>(p, row)) != SMP_ROW_GUMBEL) return;
+        if (SCHED) sample_sched_params<TRUNC>(p, row);
+        else sample_row_params<TRUNC>(p, row);
     }
     const int prow = (ROWS && p.row_seeds) ? 0 : row;   // Philox row field
     const float* lg = p.logits + (long)row * V;
@@ -2327,14 +2364,15 @@ static int launch_sample(const SampleArgs& a, hipStream_t s) {
     return rq_check_launch("sample_kernel");
 }
 
-#if defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU)
+#if defined(RQ_SAMPLE_ROWS_TU) || defined(RQ_SAMPLE_LOGP_TU) || defined(RQ_SAMPLE_TRUNC_TU) || defined(RQ_SAMPLE_SCHED_TU)
 // per-row parameters: the three kernels over all rows, each workgroup leaving at once unless the row is of its class (sample_row_class).
 // The streaming kernel cannot write probs_out and the register kernel needs V <= 16384, V % 4 == 0 and the redo workspace: where a
 // kernel can have no rows it is not launched.  The general kernel comes last (it reads the flags the register kernel wrote).  The
 // values are device arrays, so nothing about them is checked here; the kernels trap on none (temperature <= 0 or NaN draws garbage).
 // TRUNC: the rows whose two filters are off take the kernel of their class as today (the streaming kernel with or without LOGP, as
 // a.logp_out says); the register and the general kernel are the LOGP = true builds, which write where a.logp_out is given.
-template <bool GUIDED, bool LOGP = false, bool TRUNC = false>
+// SCHED: the same sequence with the scheduled kernels (the tables are indexed by position and depth; the class rule is unchanged).
+template <bool GUIDED, bool LOGP = false, bool TRUNC = false, bool SCHED = false>
 static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     if (a.V < 1 || a.V > 36000) return rq_fail(RQAMD_ERR_UNSUPPORTED, "sampler: vocab %d not in 1..36000", a.V);
     if (!a.row_top_k || !a.row_top_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: per-row top_k / top_p missing");
@@ -2342,18 +2380,18 @@ static int launch_sample_per_row(const SampleArgs& a, hipStream_t s) {
     static const bool env_lds_only = getenv("RQAMD_SAMPLER_LDS") != nullptr;      // A/B switch, as in launch_sample
     if (env_lds_only) b.redo = nullptr;
     if (!b.probs_out && b.out) {
-        auto kern = sample_gumbel_kernel<GUIDED, true, LOGP, TRUNC>;
-        if constexpr (TRUNC) { if (!b.logp_out) kern = sample_gumbel_kernel<GUIDED, true, false, true>; }
+        auto kern = sample_gumbel_kernel<GUIDED, true, LOGP, TRUNC, SCHED>;
+        if constexpr (TRUNC) { if (!b.logp_out) kern = sample_gumbel_kernel<GUIDED, true, false, true, SCHED>; }
         RQ_LAUNCH(kern, dim3(b.rows), dim3(256), 0, s, b);
         RQ_TRY(rq_check_launch("sample_gumbel_kernel (per row)"));
     }
     if (b.V <= SMP_T * SMP_VPT && b.V % 4 == 0 && b.redo) {
-        const auto kern = sample_topk_kernel<GUIDED, true, LOGP, TRUNC>;
+        const auto kern = sample_topk_kernel<GUIDED, true, LOGP, TRUNC, SCHED>;
         RQ_LAUNCH(kern, dim3(b.rows), dim3(SMP_T), 0, s, b);
         RQ_TRY(rq_check_launch("sample_topk_kernel (per row)"));
     }
     const size_t smem = (size_t)b.V * 4 + 16 * 4 + 16 * 4 + 256 * 4 + 4 * 4 + 32 * 4;
-    const auto kern = sample_kernel<GUIDED, true, LOGP, TRUNC>;
+    const auto kern = sample_kernel<GUIDED, true, LOGP, TRUNC, SCHED>;
     static RqDeviceOnce attr_once;      // kernel attributes are per device
     if (attr_once.first()) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2380,6 +2418,20 @@ int rq_launch_sample_trunc(const SampleArgs& a, hipStream_t s) {
     if (a.row_min_p || a.row_typical_p) return rq_fail(RQAMD_ERR_INVALID, "sampler: row_min_p / row_typical_p without row_temperature (null)");
     return a.logits_u ? launch_sample<true, true, true>(a, s) : launch_sample<false, true, true>(a, s);
 }
+#elif defined(RQ_SAMPLE_SCHED_TU)
+// a.sched set (engine_rqt.hip: a call armed by rqamd_rqt_sample_schedule): the per-row launch sequence over the scheduled tables, in the
+// build the call needs -- TRUNC where a min-p / typical table is given, else LOGP where the draw's log-probability is wanted, else plain
+template <bool GUIDED>
+static int launch_sample_sched(const SampleArgs& a, hipStream_t s) {
+    if (a.row_min_p || a.row_typical_p) return launch_sample_per_row<GUIDED, true, true, true>(a, s);
+    if (a.logp_out) return launch_sample_per_row<GUIDED, true, false, true>(a, s);
+    return launch_sample_per_row<GUIDED, false, false, true>(a, s);
+}
+int rq_launch_sample_sched(const SampleArgs& a, hipStream_t s) {
+    if (!a.row_temperature || !a.pos || a.row_stride < 0) return rq_fail(RQAMD_ERR_INVALID, "sampler: a schedule needs its tables and the device position");
+    if (a.min_p > 0.f || (a.typical_p >= 0.f && a.typical_p < 1.0f)) return rq_fail(RQAMD_ERR_INVALID, "sampler: a schedule takes min_p / typical_p as tables");
+    return a.logits_u ? launch_sample_sched<true>(a, s) : launch_sample_sched<false>(a, s);
+}
 #elif defined(RQ_SAMPLE_GUIDED_TU)
 int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s) { return launch_sample<true>(a, s); }
 #else
@@ -2387,6 +2439,7 @@ int rq_launch_sample_guided(const SampleArgs& a, hipStream_t s);     // rqt_samp
 int rq_launch_sample_per_row(const SampleArgs& a, hipStream_t s);    // rqt_sample_rows.hip
 int rq_launch_sample_logp(const SampleArgs& a, hipStream_t s);       // rqt_sample_logp.hip
 int rq_launch_sample(const SampleArgs& a, hipStream_t s) {
+    if (a.sched) return rq_launch_sample_sched(a, s);                   // (a scheduled engine call: the tables are indexed by position and depth)
     if (rq_sample_trunc_on(a)) return rq_launch_sample_trunc(a, s);     // (off values, no tables: everything below is as it was)
     if (a.logp_out) return rq_launch_sample_logp(a, s);
     if (a.row_temperature) return rq_launch_sample_per_row(a, s);

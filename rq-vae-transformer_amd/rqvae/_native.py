@@ -98,6 +98,8 @@ _SIGS = {
                                         C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_sample_logp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_sample_trunc': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    'rqamd_rqt_sample_schedule': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -791,11 +793,42 @@ class RqtEngine(_Engine):
         None = off.  (A method rather than an argument of the four: their argument lists stay as they are.)"""
         self._trunc = (min_p, typical_p, per_image)
 
+    SCHEDULE_PARAMETERS = ('temperature', 'top_k', 'top_p', 'guidance_scale', 'min_p', 'typical_p')
+
+    def arm_schedule(self, per_image=False, **tables):
+        """rqamd_rqt_sample_schedule for the NEXT sample / sample_masked / sample_guided / sample_rows call of this object: sampling
+        schedules over positions and depths.  Keywords of SCHEDULE_PARAMETERS, each a flat host sequence or tensor of H * W * D values in raster
+        order, depth last (per_image: B * H * W * D, image-major) or None: that parameter comes from the call's own arguments.
+        No keyword (or all None) disarms."""
+        bad = set(tables) - set(self.SCHEDULE_PARAMETERS)
+        if bad:
+            raise TypeError(f'arm_schedule: unknown parameter {sorted(bad)}')
+        self._sched = (dict(tables), bool(per_image)) if any(v is not None for v in tables.values()) else None
+
     def _sample_call(self, partial, call, want_logp, guided=False):
         """one sampling call; want_logp: armed through rqamd_rqt_sample_logp first (inside the same attempt: a failed call consumes the
-        arming) -> (draw, model, model_uncond or None), (B,H,W,D) fp32 each, else None.  An arm_trunc() before the call is passed on
-        to rqamd_rqt_sample_trunc the same way, and consumed"""
+        arming) -> (draw, model, model_uncond or None), (B,H,W,D) fp32 each, else None.  An arm_trunc() / arm_schedule() before the call
+        is passed on to rqamd_rqt_sample_trunc / rqamd_rqt_sample_schedule the same way, and consumed"""
         trunc, self._trunc = getattr(self, '_trunc', None), None
+        sched, self._sched = getattr(self, '_sched', None), None
+        if sched is not None:
+            n = self.cfg.H * self.cfg.W * self.cfg.D * (partial.shape[0] if sched[1] else 1)
+            sarrs, host = [], []                     # (host tensors: the arrays the library reads, alive until the call returns)
+            for name in self.SCHEDULE_PARAMETERS:
+                v = sched[0].get(name)
+                if v is None:
+                    sarrs.append(None)
+                    continue
+                t = torch.as_tensor(v, dtype=torch.int32 if name == 'top_k' else torch.float32, device='cpu').reshape(-1).contiguous()
+                if t.numel() != n:
+                    raise ValueError(f'arm_schedule: {name} has {t.numel()} values; expected {n}')
+                host.append(t)
+                sarrs.append(C.cast(t.data_ptr(), C.POINTER(C.c_int if name == 'top_k' else C.c_float)))
+            unscheduled = call
+
+            def call(host=host):
+                rc = self._L.rqamd_rqt_sample_schedule(self._h, *sarrs, int(sched[1]))
+                return rc if rc != 0 else unscheduled()
         if trunc is not None and (trunc[0] is not None or trunc[1] is not None):
             arrs = [None if v is None else (C.c_float * len(v))(*[float(x) for x in v]) for v in trunc[:2]]
             inner = call

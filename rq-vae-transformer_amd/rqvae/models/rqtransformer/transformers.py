@@ -132,6 +132,7 @@ class RQTransformer(Stage2Model):
         self._return_log_probs = False                   # inside `with self.return_log_probs()`: sample() also returns SampleLogProbs
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
         self._truncation = (None, None)                  # (min_p, typical_p) of the sample() calls inside `with self.truncation(...)`
+        self._schedule = None                            # {parameter: tensor} of the sample() calls inside `with self.schedule(...)`
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -413,6 +414,8 @@ class RQTransformer(Stage2Model):
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        if self._schedule:
+            return self._sample_scheduled(partial_sample, model_aux, cond, start_loc, temperature, top_k, top_p, amp, cached, keep_mask)
         want = self._want_log_probs(cached)
         trunc, force_rows = self._trunc_args(partial_sample.shape[0], *self._truncation)
         rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, force=force_rows)
@@ -755,6 +758,9 @@ class RQTransformer(Stage2Model):
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
+        if self._schedule:
+            return self._sample_scheduled(partial_sample, model_aux, cond, start_loc, temperature, top_k, top_p, amp, cached, keep_mask,
+                                          guided=True, uncond=uncond, guidance_scale=guidance_scale)
         want = self._want_log_probs(cached)
         trunc, force_rows = self._trunc_args(partial_sample.shape[0], *self._truncation)
         rows = self._per_image(partial_sample.shape[0], temperature, top_k, top_p, guidance_scale, force=force_rows)
@@ -807,6 +813,226 @@ class RQTransformer(Stage2Model):
             finally:
                 eng.arm_trunc(None, None)
         return self._with_log_probs(want, self._on_side_stream(device, run))
+
+    # ------------------------------------------------------------------ sampling schedules over positions and depths
+    SCHEDULE_PARAMETERS = ('temperature', 'top_k', 'top_p', 'guidance_scale', 'min_p', 'typical_p')
+
+    @contextlib.contextmanager
+    def schedule(self, temperature=None, top_k=None, top_p=None, guidance_scale=None, min_p=None, typical_p=None):
+        """Sampling parameters that change along the raster order (not in the reference), for the sample() / sample_guided() calls made
+        inside the block: a guidance scale that ramps up over the positions, a temperature that anneals, a tight top-k for the first
+        rows, a colder temperature at the deeper codes of some positions.  Each value is a tensor, array or nested list of shape (H, W)
+        (every depth of a position alike), (H, W, D), or (B, H, W, D) (a schedule per image), and replaces that parameter of the call:
+        passing the call a value other than the default for a scheduled parameter as well is a ValueError, as is a wrong shape, a
+        temperature that is not finite and > 0, a non-finite guidance scale / min_p / typical_p or a min_p above 1.  Code (b, h, w, d) is
+        drawn exactly as the call that gives every image's values at (b, h, w, d) as per-image values draws it there -- same logits,
+        same Philox counter -- so a schedule that is constant over the positions returns the unscheduled call's codes.  top_k / top_p /
+        min_p / typical_p use their off values as in the per-image tensors (top_k >= vocab_size, top_p >= 1, min_p <= 0, typical_p >= 1).
+        Parameters that are not scheduled keep every form they have (number, per-depth list, per-image tensor).  Everything runs inside
+        the engine, on captured graphs whose keys hold no value (another schedule replays them), and composes with keep_mask, start_loc,
+        amp, use_graph, prefix_mode, seeds(), return_log_probs() (draw: the log-probability after all stages, with the position's values)
+        and truncation(); ``cached=False`` returns the cached call's codes; ``sampler='torch'`` raises NotImplementedError.
+        position_ramp() makes the usual ramps.  (A context rather than arguments, like seeds(): the argument lists stay as they are.)"""
+        given = dict(temperature=temperature, top_k=top_k, top_p=top_p, guidance_scale=guidance_scale, min_p=min_p, typical_p=typical_p)
+        saved, self._schedule = self._schedule, {k: v for k, v in given.items() if v is not None}
+        try:
+            yield self
+        finally:
+            self._schedule = saved
+
+    def position_ramp(self, start, end, kind='linear'):
+        """(H, W) fp32 tensor that goes from `start` at the first position to `end` at the last one along the raster order: 'linear',
+        or 'cosine' (half a cosine period: flat at both ends).  Both end points are exact and the ramp is monotonic."""
+        (H, W, _) = self.block_size
+        n = H * W
+        t = torch.arange(n, dtype=torch.float64) / max(n - 1, 1)
+        if kind == 'cosine':
+            t = (1.0 - torch.cos(math.pi * t)) / 2.0
+        elif kind != 'linear':
+            raise ValueError(f"position_ramp: kind = {kind!r} ('linear' or 'cosine')")
+        ramp = (float(start) + (float(end) - float(start)) * t).to(torch.float32)
+        ramp[0] = float(start)
+        if n > 1:
+            ramp[-1] = float(end)
+        return ramp.view(H, W)
+
+    def _schedule_values(self, B, guided):
+        """self._schedule, checked -> ({parameter: (1 or B, H*W, D) tensor on the host, top_k int64 and the others fp32, clipped and with
+        the off values of the per-image tables}, is one of them per image?)"""
+        (H, W, D) = self.block_size
+        out, per_image = {}, False
+        for name, v in self._schedule.items():
+            t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+            if t.dtype.is_complex or t.dtype == torch.bool:
+                raise ValueError(f'schedule: {name} of dtype {t.dtype}; expected real values')
+            if name == 'top_k':
+                if t.dtype.is_floating_point:
+                    raise ValueError(f'schedule: top_k of dtype {t.dtype}; expected integers')
+                t = t.to(torch.int64)
+            else:
+                t = t.to(torch.float32)
+            shp = tuple(t.shape)
+            if shp == (H, W):
+                t = t.reshape(1, H * W, 1).expand(1, H * W, D)
+            elif shp == (H, W, D):
+                t = t.reshape(1, H * W, D)
+            elif shp == (B, H, W, D):
+                t, per_image = t.reshape(B, H * W, D), True
+            else:
+                raise ValueError(f'schedule: {name} of shape {shp}; expected {(H, W)}, {(H, W, D)} or {(B, H, W, D)}')
+            if name == 'guidance_scale' and not guided:
+                raise ValueError('schedule: a guidance_scale schedule needs sample_guided()')
+            if name != 'top_k' and not bool(torch.isfinite(t).all()):
+                if name != 'top_p' or bool(torch.isnan(t).any()):
+                    raise ValueError(f'schedule: {name} holds a non-finite value')
+            if name == 'temperature' and not bool((t > 0).all()):
+                raise ValueError('schedule: every temperature must be > 0 and finite')
+            if name == 'min_p':
+                if bool((t > 1.0).any()):
+                    raise ValueError('schedule: min_p must be at most 1')
+                t = torch.where(t > 0, t, torch.zeros_like(t))
+            if name == 'typical_p':
+                t = torch.where((t >= 0) & (t < 1.0), t, torch.full_like(t, -1.0))
+            if name == 'top_k':
+                t = torch.minimum(t, torch.tensor(self.vocab_size, dtype=torch.int64))      # (as _filter_lists: >= vocab_size is off)
+            if name == 'top_p':
+                t = t.clamp(max=1.0)
+            out[name] = t.contiguous()
+        return out, per_image
+
+    def _sample_scheduled(self, partial_sample, model_aux, cond, start_loc, temperature, top_k, top_p, amp, cached, keep_mask,
+                          guided=False, uncond=None, guidance_scale=1.0):
+        """sample() / sample_guided() inside ``with self.schedule(...)``: rqamd_rqt_sample_schedule in front of the entry point the
+        unscheduled parameters ask for, or -- cached=False -- the uncached loop over the per-row stand-alone samplers"""
+        (H, W, D) = self.block_size
+        B = partial_sample.shape[0]
+        device = partial_sample.device
+        if self.sampler == 'torch':
+            raise NotImplementedError("schedule() runs in the on-device sampler; sampler='torch' draws with torch.multinomial from one set "
+                                      'of values per call')
+        want = self._want_log_probs(cached)
+        sched, sched_per_image = self._schedule_values(B, guided)
+        min_p, typical_p = self._truncation
+        call = dict(temperature=(temperature, lambda v: isinstance(v, (int, float)) and float(v) == 1.0), top_k=(top_k, lambda v: v is None),
+                    top_p=(top_p, lambda v: v is None), min_p=(min_p, lambda v: v is None), typical_p=(typical_p, lambda v: v is None),
+                    guidance_scale=(guidance_scale, lambda v: isinstance(v, (int, float)) and float(v) == 1.0))
+        for name in sched:
+            value, is_default = call[name]
+            if not is_default(value):
+                raise ValueError(f'{name} is scheduled (schedule()) and given to the call as well')
+        if 'min_p' in sched:
+            min_p = None
+        if 'typical_p' in sched:
+            typical_p = None
+        trunc, force_rows = self._trunc_args(B, min_p, typical_p)
+        rows = self._per_image(B, temperature, top_k, top_p, guidance_scale if guided else None, force=force_rows)
+        top_k_list, top_p_list = (None, None) if rows is not None else self._filter_lists(top_k, top_p)
+        if guided:
+            if uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
+                raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+            if rows is None and not math.isfinite(float(guidance_scale)):
+                raise ValueError(f'guidance_scale {guidance_scale} is not finite')
+        eng = self._sampling_eng(amp)
+        cbs = self._checked_codebooks(model_aux)
+        xs = partial_sample.to(torch.long).contiguous()
+        c = self._cond(cond, B, device)
+        u = self._cond(uncond, B, device) if guided else None
+        keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
+        seeded = rows is not None and rows['seeds'] is not None
+        seed, offset = (0, 0) if seeded else self._draw_rng(device, H * W * D)
+        if not cached:
+            return self._sample_uncached_scheduled(eng, xs, c, u, cbs, start_loc, sched, rows, trunc, temperature, top_k_list, top_p_list,
+                                                   guidance_scale if guided else None, seed, offset, keep, active)
+        nb = B if sched_per_image else 1
+        arrays = {name: t.expand(nb, H * W, D).reshape(-1) for name, t in sched.items()}
+        tr = self._trunc_engine(trunc)
+        keep8, pos_active, start = None, None, start_loc
+        if keep is not None:
+            keep8 = keep.to(torch.uint8).contiguous()
+            pos_active = [bool(a) for a in active.any(dim=1).tolist()]
+            start = (0, 0)                                                   # (the kept prefix is part of `keep`)
+
+        def run():
+            eng.arm_schedule(per_image=sched_per_image, **arrays)
+            if tr:
+                eng.arm_trunc(*tr)
+            try:
+                if rows is not None:
+                    return eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None,
+                                           rows['seeds'], seed, offset, self.use_graph, **want)
+                if guided:
+                    return eng.sample_guided(xs, keep8, pos_active, c, u, cbs, start, temperature, float(guidance_scale), top_k_list, top_p_list,
+                                             seed, offset, self.use_graph, **want)
+                if keep is not None:
+                    return eng.sample_masked(xs, keep8, pos_active, c, cbs, temperature, top_k_list, top_p_list, seed, offset, self.use_graph, **want)
+                return eng.sample(xs, c, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, self.use_graph, **want)
+            finally:
+                eng.arm_trunc(None, None)            # (a call refused before it reached the library leaves nothing armed)
+                eng.arm_schedule()
+        return self._with_log_probs(want, self._on_side_stream(device, run))
+
+    def _sample_uncached_scheduled(self, eng, xs, cond, uncond, cbs, start_loc, sched, rows, trunc, temperature, top_k_list, top_p_list,
+                                   guidance_scale, seed, offset, keep, active):
+        """``cached=False`` inside schedule(): _sample_uncached with the values of every step sliced out of the tables the engine fills
+        for the cached call -- the schedule where it gives a parameter, else the call's own values, broadcast -- and drawn by
+        sample_logits_rows (sample_logits_trunc where a min-p / typical value is on anywhere).  Equal to the cached call bit for bit."""
+        (H, W, D) = self.block_size
+        B, device = xs.shape[0], xs.device
+        guided = guidance_scale is not None
+
+        def full(name, fallback, dtype):
+            """(B, H*W, D): the schedule, or the call's values -- 1 or B rows of 1 or D values -- broadcast over the positions"""
+            if name in sched:
+                return sched[name].expand(B, H * W, D).to(dtype)
+            return torch.tensor(fallback, dtype=dtype)[:, None, :].expand(B, H * W, D)
+        if rows is not None:
+            T = full('temperature', [[t] for t in rows['T']], torch.float32)
+            K = full('top_k', rows['tk'], torch.int32)
+            P = full('top_p', rows['tp'], torch.float32)
+            G = full('guidance_scale', [[g] for g in rows['gs']], torch.float32) if guided else None
+        else:
+            T = full('temperature', [[float(temperature)]], torch.float32)
+            K = full('top_k', [top_k_list], torch.int32)
+            P = full('top_p', [top_p_list], torch.float32)
+            G = full('guidance_scale', [[float(guidance_scale)]], torch.float32) if guided else None
+        mp_rows = [[0.0] * D] if trunc is None else trunc['mp'] if trunc['per_image'] else [trunc['mp']]
+        ty_rows = [[-1.0] * D] if trunc is None else trunc['ty'] if trunc['per_image'] else [trunc['ty']]
+        Mp, Ty = full('min_p', mp_rows, torch.float32), full('typical_p', ty_rows, torch.float32)
+        any_trunc = bool((Mp > 0).any()) or bool((Ty >= 0).any())
+        T, K, P, Mp, Ty = (t.contiguous().to(device) for t in (T, K, P, Mp, Ty))
+        sd = rows['seeds'] if rows is not None else None
+        seeds_dev = None if sd is None else torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in sd], dtype=torch.int64, device=device)
+        start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
+        if keep is not None:
+            xs = torch.where(keep, xs, torch.zeros_like(xs))                # (see sample(): the host loops embed every code)
+        xs2, c2 = xs.clone(), cond
+        if guided:
+            xs2 = torch.cat([xs, xs])
+            if cond is not None or uncond is not None:
+                zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
+                c2 = torch.cat([zeros if cond is None else cond, zeros if uncond is None else uncond])
+        for pos in range(start, H * W):
+            h, w = divmod(pos, W)
+            for d in range(D):
+                if active is not None and not active[pos, d]:
+                    continue                             # keep_mask: the code is given in every row
+                logits = self._on_side_stream(device, lambda: eng.logits(xs2, c2, cbs))[:, h, w, d].contiguous()
+                if self.vocab_size[d] < logits.shape[-1]:
+                    logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
+                if guided:
+                    logits = self._guide_rows(logits[:B], logits[B:], G[:, pos, d].tolist())
+                step = dict(seed=seed, offset=offset + pos * D + d)
+                tkd = (T[:, pos, d].contiguous(), K[:, pos, d].contiguous(), P[:, pos, d].contiguous())
+                if any_trunc:
+                    idx = _native.sample_logits_trunc(logits, row_temperature=tkd[0], row_top_k=tkd[1], row_top_p=tkd[2],
+                                                      row_min_p=Mp[:, pos, d].contiguous(), row_typical_p=Ty[:, pos, d].contiguous(),
+                                                      row_seeds=seeds_dev, **step)[0]
+                else:
+                    idx, _ = _native.sample_logits_rows(logits, *tkd, seeds=seeds_dev, **step)
+                if keep is not None:
+                    idx = torch.where(keep[:, h, w, d], xs2[:B, h, w, d], idx)
+                xs2[:, h, w, d] = torch.cat([idx, idx]) if guided else idx
+        return xs2[:B].contiguous() if guided else xs2
 
     def _keep_flags(self, keep_mask, xs, start_loc):
         """keep_mask of sample() -> (keep (B,H,W,D) bool on the device of `xs`, active (H*W, D) bool on the host: some row draws that
