@@ -352,6 +352,26 @@ int rqamd_rqt_sample_trunc(rqamd_rqt* h, const float* min_p, const float* typica
  * hold no value: another schedule replays the same graphs, and scheduled, per-image and scalar calls never recapture each other's. */
 int rqamd_rqt_sample_schedule(rqamd_rqt* h, const float* temperature, const int* top_k, const float* top_p,
                               const float* guidance_scale, const float* min_p, const float* typical_p, int per_image);
+/* Shared-prompt sampling (N images per prompt on one cached text prefix; not in the reference); additive, ABI v7.  Arms the NEXT
+ * rqamd_rqt_sample, _masked, _guided or _rows call on the handle; that call consumes the arming whether it succeeds or fails.
+ * fan = 0 disarms.  In the armed call `batch` = G * fan rows, `cond` / `uncond` hold G = batch / fan rows; row r belongs to group
+ * r / fan (guided: the unconditional twin batch + r to group G + r / fan).  Row r is drawn as the unarmed call with every cond row
+ * repeated fan times draws it: the same decode-step, sampler and Philox launches over `batch` rows.  Only the prefix keys and values
+ * differ in origin: they come out of a prefill over G * (block_size_cond - 1) rows instead of batch * (block_size_cond - 1), so the
+ * codes are bit-identical wherever the two prefills fall into one GEMM regime and differ only where a draw was close
+ * elsewhere.  The body stack's KV workspace is then laid out as one group cache of block_size_cond - 1 slots per (group, head) --
+ * ordinary cached memory -- plus H * W own slots per (row, head); the decode attention of the body stack reads the group's slots
+ * from the one copy (csrc/rqt_attn_shared.hip).  A handle's KV workspace has one layout at a time: a call in the other form re-lays it
+ * and drops the captured graphs.  Shared calls replay graph sets of their own; a second shared call with other prompts captures
+ * nothing.  The text prefix always goes through the shared prefill; given code positions are stepped, whatever "prefix.one_pass"
+ * says.  It composes with rqamd_rqt_sample_logp, _trunc and _schedule.
+ * Refused before anything is enqueued: fan < 0 or batch % fan != 0: RQAMD_ERR_INVALID; block_size_cond < 2 (nothing to share),
+ * RQAMD_KV=int8k / int8kv, a body context over 256 or a body head size other than 64: RQAMD_ERR_UNSUPPORTED. */
+int rqamd_rqt_sample_shared(rqamd_rqt* h, int fan);
+/* *bytes = the device bytes currently reserved for the KV caches of the handle (0 before the first batch).  A reservation, not the need
+ * of the last call: within one layout the caches only grow, so after shared calls the figure covers the largest batch and the largest
+ * group count seen since the layout was last laid out (a call in the other form starts again from its own sizes). */
+int rqamd_rqt_kv_bytes(rqamd_rqt* h, int64_t* bytes);
 /* *captures = the number of position graphs this handle has captured so far (every form of sampling); a call that replays only
  * leaves it unchanged. */
 int rqamd_rqt_graph_captures(rqamd_rqt* h, int64_t* captures);
@@ -499,6 +519,16 @@ int rqamd_dbg_rqt_attn_prefill(const void* qkv, void* kc, void* vc, float* ksc, 
 /* Causal attention inside groups of `group` consecutive rows (the depth axis of the head stack): qkv [rows][3E] -> y [rows][E].
  * Refused with RQAMD_ERR_INVALID: a null qkv or y, E not a multiple of nh, group outside 1 .. 8, rows not a multiple of group. */
 int rqamd_dbg_rqt_attn_packed(const void* qkv, int rows, int group, int nh, int E, void* y, void* stream);
+/* The decode attention of shared-prompt sampling alone (csrc/rqt_attn_shared.hip), in the style of rqamd_dbg_rqt_attn_decode.  The `fan`
+ * consecutive rows of a group share the read-only caches kc_shared, vc_shared [rows / fan][nh][Ps][64]; the own caches kc, vc are
+ * [rows][nh][Tcap_row][64].  Global key j < Ps is the group's row j, key j >= Ps own row j - Ps; this token (global index t) is appended
+ * at own row t - Ps and attends over keys 0 .. t.  Output and appended rows are bit for bit those of rqamd_dbg_rqt_attn_decode on caches
+ * [rows][nh][Ps + Tcap_row][64] that hold a copy of the group's prefix in front of each row's own positions.  t_max (-1 = Ps + Tcap_row - 1),
+ * step_dev and step_base as above.  Refused with
+ * RQAMD_ERR_INVALID before any launch: a null pointer, rows, fan, nh, E, Ps or Tcap_row < 1, rows % fan != 0, t < Ps, t - Ps >= Tcap_row,
+ * t_max >= Ps + Tcap_row, 0 <= t_max < t; with RQAMD_ERR_UNSUPPORTED: a head size other than 64, Ps + Tcap_row > 256. */
+int rqamd_dbg_rqt_attn_shared(const void* qkv, const void* kc_shared, const void* vc_shared, void* kc, void* vc, int rows, int fan, int nh,
+                              int E, int Ps, int Tcap_row, int t, int t_max, int* step_dev, int step_base, void* y, void* stream);
 
 /* Kernel variants are selected by the number of rows (batch).  factor > 1 makes the selection logic see rows * factor, so
  * that the large-batch variants run on test-sized inputs (results must not change); 1 restores normal behaviour. */

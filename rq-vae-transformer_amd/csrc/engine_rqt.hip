@@ -30,6 +30,7 @@ struct RqtLayer {
     bf16_t *wqkv, *wproj, *wfc1, *wfc2;
     float *bqkv, *bproj, *bfc1, *bfc2, *ln1w, *ln1b, *ln2w, *ln2b;
     bf16_t *kc, *vc;   // KV cache (workspace, per batch capacity)
+    bf16_t *kcs = nullptr, *vcs = nullptr;   // body layers in the shared-prompt layout (rqamd_rqt_sample_shared): the group caches [groups][nh][P][64]; else null
     float* ksc;        // body layers with the opt-in 8-bit key cache (RQAMD_KV=int8k / int8kv): per-key scales, `kc` then holds bytes; else null
     float* vsc;        // body layers with RQAMD_KV=int8kv: per-value-row scales, `vc` then holds bytes; else null
     int nh;            // attention heads of the layer's stack (body: cfg.n_head; head: the same unless the "head.n_head" option says otherwise)
@@ -110,6 +111,15 @@ struct rqamd_rqt {
     DevBuf sch_image_buf;
     size_t sch_image_rows = 0;      // images the tables of sch_image hold
     std::vector<char> sch_host;     // host staging of the tables, like row_host
+    // shared-prompt sampling (rqamd_rqt_sample_shared): the arming, and the layout of the KV workspace.  kv_groups == 0: the plain layout
+    // (body caches of Tbody slots per (row, head) in h->kv).  kv_groups > 0: the shared layout -- body caches of HW own slots per (row, head)
+    // in h->kv, and group caches of P = cond_len - 1 slots per (group, head) for up to kv_groups groups in h->kvg.  h->kvg is ordinary cached
+    // memory: every line of it is read `fan` times per position and again at the next one, where h->kv is written once and read once per
+    // position (uncached).  One layout at a time: a call in the other form re-lays the workspace (ensure_batch), which drops every graph.
+    int shared_fan = 0;
+    int cur_fan = 0;       // rows per group of the shared-prompt call being run (the body stack's attention launches read it)
+    int kv_groups = 0;
+    DevBuf kvg;
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -140,9 +150,11 @@ struct rqamd_rqt {
     static constexpr int NGRAPH = 33;
     static constexpr int NFAM_SCHED0 = 24;         // first scheduled family
     static constexpr int NFAM = 56;
-    hipGraphExec_t gexec[2 * NFAM][NGRAPH] = {};
-    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; } gkey[NFAM];
-    bool gkey_set[NFAM] = {}, gstale[NFAM] = {};
+    // Shared-prompt calls (rqamd_rqt_sample_shared: another attention launch in the body stack, other cache addresses) are every family
+    // once more, keys NFAM .. 2 * NFAM - 1 and sets 2 * NFAM .. 4 * NFAM - 1 (graph_family); the group size is part of their key.
+    hipGraphExec_t gexec[4 * NFAM][NGRAPH] = {};
+    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; int fan; int fan_pad; } gkey[2 * NFAM];
+    bool gkey_set[2 * NFAM] = {}, gstale[2 * NFAM] = {};
     bool gvalid = false;
     int64_t n_capture = 0;     // position graphs captured over the life of the handle (rqamd_rqt_graph_captures)
 
@@ -175,6 +187,13 @@ __global__ void bias_table_kernel(const float* bias, float scale, const float* p
 }
 __global__ void set_rng_kernel(uint64_t* rng, uint64_t seed, uint64_t offset) {
     if (threadIdx.x == 0) { rng[0] = seed; rng[1] = offset; }
+}
+// dst row r = src row r / fan (rows of `len` words): the conditioning of a shared-prompt call, one row per group, for every row of the batch
+__global__ void repeat_rows_kernel(const int64_t* src, int64_t* dst, long rows, int len, int fan) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= rows * len) return;
+    const long r = gid / len;
+    dst[gid] = src[(r / fan) * len + (gid - r * len)];
 }
 __global__ void fill_f32_kernel(float* p, float v, long n) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -443,15 +462,20 @@ static int prefill_chunk(const rqamd_rqt* h, int B) {
     return pc < B ? pc : B;
 }
 
-static int ensure_batch(rqamd_rqt* h, int B) {
-    if (B <= h->cap) return RQAMD_OK;
+// groups == 0: the plain layout of the KV workspace.  groups > 0 (a shared-prompt call of that many groups): the shared layout
+static int ensure_batch(rqamd_rqt* h, int B, int groups = 0) {
+    const bool relay = (groups > 0) != (h->kv_groups > 0);      // the other layout: everything is laid out again, for exactly B rows
+    if (B <= h->cap && !relay && groups <= h->kv_groups) return RQAMD_OK;
     // Failure-atomic regrowth: the old capacity is dropped BEFORE anything is freed, and the new one is recorded only after
     // every allocation succeeded -- a failed hipMalloc (the KV cache is ~135 GB at B = 8192) leaves the handle empty
     // (cap 0, no graphs), never pointing at freed memory; the caller may retry with a smaller batch.
+    if (!relay && B < h->cap) B = h->cap;                          // (more groups only: the rows stay)
     h->cap = 0;
+    h->kv_groups = 0;
     h->gvalid = false;
-    for (auto& L : h->body) { L.kc = L.vc = nullptr; L.ksc = L.vsc = nullptr; }
+    for (auto& L : h->body) { L.kc = L.vc = nullptr; L.ksc = L.vsc = nullptr; L.kcs = L.vcs = nullptr; }
     for (auto& L : h->head) { L.kc = L.vc = nullptr; L.ksc = L.vsc = nullptr; }
+    if (relay) { h->kv.release(); h->kvg.release(); }              // rqamd_rqt_kv_bytes reports what the layout in force needs
     const size_t E = h->E, V = h->V;
     const size_t brows = (size_t)B;
     const size_t prow = (size_t)prefill_chunk(h, B) * (h->cond_len - 1);
@@ -484,7 +508,8 @@ static int ensure_batch(rqamd_rqt* h, int B) {
         t.T = (float*)take(sb); t.tk = (int*)take(sb); t.tp = (float*)take(sb); t.gs = (float*)take(sb); t.mp = (float*)take(sb); t.typ = (float*)take(sb);
     }
     // KV caches: body [rows][nh][Tbody][64] x2 per layer, head Tcap = D
-    const size_t kvb = al(brows * E * h->Tbody * 2), kvh = al(brows * E * h->D * 2);
+    // (shared layout, bf16 / fp16 only: HW own slots per (row, head); the P prefix slots live once per group in h->kvg)
+    const size_t kvb = al(brows * E * (groups > 0 ? h->HW : h->Tbody) * 2), kvh = al(brows * E * h->D * 2);
     // (8-bit keys: half the bytes for K plus one fp32 scale per (row, head, position))
     const size_t kkb = h->kv_int8k ? al(brows * E * h->Tbody) : kvb, ksb = h->kv_int8k ? al(brows * (E / 64) * h->Tbody * 4) : 0;
     const size_t vvb = h->kv_int8v ? kkb : kvb, vsb = h->kv_int8v ? ksb : 0;
@@ -500,6 +525,13 @@ static int ensure_batch(rqamd_rqt* h, int B) {
         L.vsc = h->kv_int8v ? (float*)q : nullptr; q += vsb;
     }
     for (auto& L : h->head) { L.kc = (bf16_t*)q; q += kvh; L.vc = (bf16_t*)q; q += kvh; L.ksc = L.vsc = nullptr; }
+    if (groups > 0) {
+        const size_t gb = al((size_t)groups * E * (h->cond_len - 1) * 2);
+        RQ_TRY(h->kvg.reserve(2 * gb * h->body.size()));
+        char* g = (char*)h->kvg.p;
+        for (auto& L : h->body) { L.kcs = (bf16_t*)g; g += gb; L.vcs = (bf16_t*)g; g += gb; }
+    }
+    h->kv_groups = groups;
     h->cap = B;
     return RQAMD_OK;
 }
@@ -563,7 +595,8 @@ struct Pending { const float* slabs; int n; const float* bias; };   // un-reduce
 
 // one transformer block on `rows` single-token rows; x is the fp32 residual stream (updated lazily:
 // `pend` carries the previous block's fc2 partials + bias into this block's first resid_ln)
-struct PrefillCtx { int img0, n_img, P; };   // non-null: `rows` = n_img * P prefix tokens of images img0.. (multi-token causal attention)
+struct PrefillCtx { int img0, n_img, P; bool group = false; };   // non-null: `rows` = n_img * P prefix tokens of images img0.. (multi-token causal attention)
+// group (a shared-prompt call): the "images" are groups and their keys / values go to the group caches (L.kcs / L.vcs, capacity P = Tcap)
 // one-pass forward, non-null: `rows` = n_seq sequences of T consecutive rows, causal attention inside each, no KV cache.
 // packed: the head stack's depth groups (T <= 8, a lane per query); else the body stack's (image, token) rows (a lane per query of a
 // wavefront per (image, head), K / V staged in LDS)
@@ -596,19 +629,29 @@ static int run_block(rqamd_rqt* h, RqtLayer& L, float* x_in, float* x, Pending& 
         // (8-bit keys: a key is 64 bytes, i.e. half the bf16 stride, and has one scale)
         ap.kc = L.ksc ? (bf16_t*)((unsigned char*)L.kc + pf->img0 * img_stride) : L.kc + pf->img0 * img_stride;
         ap.ksc = L.ksc ? L.ksc + (long)pf->img0 * L.nh * Tcap : nullptr;
+        if (pf->group) { ap.kc = L.kcs + pf->img0 * img_stride; ap.vc = L.vcs + pf->img0 * img_stride; ap.ksc = ap.vsc = nullptr; }
         ap.n_img = pf->n_img; ap.P = pf->P; ap.nh = L.nh; ap.E = E; ap.Tcap = Tcap;
         RQ_TRY(rq_launch_attn_prefill(ap, st));
     } else {
-        AttnDecodeArgs at{};
-        at.qkv = h->qkv; at.kc = L.kc; at.vc = L.vc; at.ksc = L.ksc; at.vsc = L.vsc; at.y = h->ya; at.step = step; at.step_off = step_off;
-        at.t_max = t_max; at.rows = rows; at.nh = L.nh; at.E = E; at.Tcap = Tcap;
         GemmProfile& pfl = h->prof;
         if (pfl.on) {
             if (pfl.used_attn + 2 > pfl.ev_attn.size())
                 for (int i = 0; i < 2; ++i) { hipEvent_t e; RQ_HIP(hipEventCreate(&e)); pfl.ev_attn.push_back(e); }
             RQ_HIP(hipEventRecord(pfl.ev_attn[pfl.used_attn], st));
         }
-        RQ_TRY(rq_launch_attn_decode(at, st));
+        if (L.kcs) {
+            // shared-prompt layout (body layers only): the prefix keys come from the group's one copy; the own caches hold HW slots per row (run_block's `Tcap` is
+            // not used here)
+            AttnSharedArgs as{};
+            as.qkv = h->qkv; as.kcs = L.kcs; as.vcs = L.vcs; as.kc = L.kc; as.vc = L.vc; as.y = h->ya; as.step = step; as.step_off = step_off;
+            as.t_max = t_max; as.rows = rows; as.fan = h->cur_fan; as.nh = L.nh; as.E = E; as.Ps = h->cond_len - 1; as.Tcap = h->HW;
+            RQ_TRY(rq_launch_attn_shared(as, st));
+        } else {
+            AttnDecodeArgs at{};
+            at.qkv = h->qkv; at.kc = L.kc; at.vc = L.vc; at.ksc = L.ksc; at.vsc = L.vsc; at.y = h->ya; at.step = step; at.step_off = step_off;
+            at.t_max = t_max; at.rows = rows; at.nh = L.nh; at.E = E; at.Tcap = Tcap;
+            RQ_TRY(rq_launch_attn_decode(at, st));
+        }
         if (pfl.on) { RQ_HIP(hipEventRecord(pfl.ev_attn[pfl.used_attn + 1], st)); pfl.used_attn += 2; }
     }
     int ns = 1;
@@ -643,6 +686,7 @@ struct StepCtx {
     const float* typical_p; //  calls read h->row_mp / h->row_typ at every depth
     bool sched;            // scheduled call (rqamd_rqt_sample_schedule): the scheduled per-row samplers read EVERY parameter at (row, position, depth) from
     bool sched_per_image;  //   h->sch_image (a schedule per image) or h->sch_shared (one for all rows); trunc: the min-p / typical tables are read too
+    int fan;               // shared-prompt call (rqamd_rqt_sample_shared): rows per group, `cond` / `uncond` hold B / fan (guided: Bs / fan) rows; 0: a plain call
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
 };
@@ -778,6 +822,9 @@ static int step_family(const StepCtx& c) {
     return (c.trunc ? 12 : 0) + (c.logp ? 6 : 0) + (c.per_row ? (c.row_seeds ? 4 : 2) : 0) + (c.guided ? 1 : 0);
 }
 
+// the key / graph-set family of a call: shared-prompt calls have every family of step_family once more
+static int graph_family(const StepCtx& c) { return step_family(c) + (c.fan ? rqamd_rqt::NFAM : 0); }
+
 // everything that happens at one spatial position (position read from h->st[0] on the device)
 static int position_sequence(rqamd_rqt* h, const StepCtx& c, bool first_pos, bool do_head, int host_pos, hipStream_t st) {
     Pending pend;
@@ -795,11 +842,45 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
                        bool skip_text = false) {
     const int B = c.B;
     h->step_on = false;                            // any new batch ends a stepping sequence (same workspace)
-    RQ_TRY(ensure_batch(h, B));
-    RQ_TRY(finalize_tables(h, st));
     const int n_in = c.guided ? c.Bs : B;          // rows the caller gave
-    const size_t xb = (size_t)n_in * h->HW * h->D * 8, cb = (size_t)n_in * h->cond_len * 8;
+    const int n_grp = c.fan ? n_in / c.fan : 0;    // shared-prompt call: rows of `cond` / `uncond`; the prefix runs over n_grp (guided: 2 n_grp) groups
+    const int groups = c.guided ? 2 * n_grp : n_grp;
+    RQ_TRY(ensure_batch(h, B, groups));
+    RQ_TRY(finalize_tables(h, st));
+    h->cur_fan = c.fan;
+    const size_t xb = (size_t)n_in * h->HW * h->D * 8, cb = (size_t)(c.fan ? n_grp : n_in) * h->cond_len * 8;
     RQ_HIP(hipMemcpyAsync(h->xs, partial, xb, hipMemcpyDeviceToDevice, st));
+    if (c.fan) {
+        // Shared-prompt call: h->cond holds one row per group first (cond, then uncond) and the P text tokens of the `groups` groups go
+        // through the body stack into the group caches -- the loop below over groups instead of rows, capacity P.  Then h->cond is
+        // filled again with a row per engine row, for the token of position 0 (position_body).
+        const int P = h->cond_len - 1, vc = h->cfg.vocab_size_cond < 1 ? 1 : h->cfg.vocab_size_cond;
+        if (cond) RQ_HIP(hipMemcpyAsync(h->cond, cond, cb, hipMemcpyDeviceToDevice, st));
+        else RQ_HIP(hipMemsetAsync(h->cond, 0, cb, st));
+        if (c.guided) {
+            if (uncond) RQ_HIP(hipMemcpyAsync(h->cond + (size_t)n_grp * h->cond_len, uncond, cb, hipMemcpyDeviceToDevice, st));
+            else RQ_HIP(hipMemsetAsync(h->cond + (size_t)n_grp * h->cond_len, 0, cb, st));
+            RQ_HIP(hipMemcpyAsync(h->xs + (size_t)n_in * h->HW * h->D, partial, xb, hipMemcpyDeviceToDevice, st));
+        }
+        RQ_TRY(rq_launch_set_int(h->st, 0, st));
+        const int pc = prefill_chunk(h, groups);
+        for (int b0 = 0; b0 < groups; b0 += pc) {
+            PrefillCtx pf{b0, groups - b0 < pc ? groups - b0 : pc, P, true};
+            RQ_TRY(rq_launch_cond_embed_multi(h->cond + (long)b0 * h->cond_len, h->cond_len, P, h->cond_emb, vc, h->pos_cond, h->x, pf.n_img, h->E, st));
+            Pending pend{nullptr, 0, nullptr};
+            h->cur_gelu_v2 = h->cfg.gelu_v2 == 1 || h->cfg.gelu_v2 == 3;
+            for (auto& L : h->body) RQ_TRY(run_block(h, L, h->x, h->x, pend, nullptr, pf.n_img * P, nullptr, 0, 0, P, st, &pf));
+        }
+        const size_t rb = (size_t)n_in * h->cond_len * 8;
+        const long nw = (long)n_in * h->cond_len;
+        const int64_t* src[2] = {cond, c.guided ? uncond : nullptr};
+        for (int half = 0; half < (c.guided ? 2 : 1); ++half) {
+            int64_t* dst = h->cond + (size_t)half * n_in * h->cond_len;
+            if (src[half]) RQ_LAUNCH(repeat_rows_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, src[half], dst, (long)n_in, h->cond_len, c.fan);
+            else RQ_HIP(hipMemsetAsync(dst, 0, rb, st));
+        }
+        return rq_check_launch("repeat_rows_kernel");
+    }
     if (cond) RQ_HIP(hipMemcpyAsync(h->cond, cond, cb, hipMemcpyDeviceToDevice, st));
     else RQ_HIP(hipMemsetAsync(h->cond, 0, cb, st));
     if (c.guided) {
@@ -850,7 +931,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
     // "prefix.one_pass": n0 = the leading positions whose codes are given in every row (before start_idx, or promised away by pos_active).
     // Their tokens -- and the text tokens before them -- go through the body stack in one pass, and the loop below starts at n0
     int n0 = 0;
-    if (h->prefix_one_pass && c.sample)
+    if (h->prefix_one_pass && c.sample && !c.fan)      // (a shared-prompt call steps its code prefix: the text prefix is the shared prefill's)
         while (n0 < n_pos && (n0 < start_idx || (pos_active && !pos_active[n0]))) ++n0;
     RQ_TRY(begin_batch(h, c, partial, cond, st, uncond, n0 >= 1));
     if (keep) {
@@ -866,7 +947,7 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
         RQ_LAUNCH(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->logp_model, __builtin_nanf(""), n);
         RQ_TRY(rq_check_launch("fill_f32_kernel"));
     }
-    const int fam = step_family(c);
+    const int fam = graph_family(c);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
     for (int pos = n0; pos < n_pos; ++pos) {
         const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
@@ -934,7 +1015,7 @@ static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
 }
 struct ArmGuard {          // an entry point that returns before sample_impl still consumes the armings
     rqamd_rqt* h;
-    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; } }
+    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; h->shared_fan = 0; } }
 };
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
@@ -950,6 +1031,15 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     h->tarm = {};
     const rqamd_rqt::SchedArm sarm = h->sarm;
     h->sarm = {};
+    const int fan = h->shared_fan;
+    h->shared_fan = 0;
+    if (fan) {             // a shared-prompt call (rqamd_rqt_sample_shared): refused here, before anything is enqueued
+        if (fan < 0 || batch % fan) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_shared: batch %d is not a multiple of the group size %d", batch, fan);
+        if (h->cfg.block_size_cond < 2) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_shared: block_size_cond = %d: no text prefix to share", h->cfg.block_size_cond);
+        if (h->kv_int8k) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_shared: RQAMD_KV=%s (the shared attention reads bf16 / fp16 caches)", h->kv_int8v ? "int8kv" : "int8k");
+        if (h->Tbody > 256) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_shared: body context %d > 256", h->Tbody);
+        if (h->E != h->cfg.n_head * 64) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_shared: body head size %d (64 only)", h->E / h->cfg.n_head);
+    }
     if (arm.model_u && !guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_logp: model_logp_uncond_out armed for an unguided call");
     // min-p / typical values of the call: tr_mp / tr_typ hold D values (scalar calls) or batch * D (per-row calls: a D-entry arming is
     // repeated for every image), off values where a filter is not given.  Scalar calls whose every value is off are unarmed calls.
@@ -986,9 +1076,10 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
         }
     }
     const int rows = guided ? 2 * batch : batch;
-    RQ_TRY(ensure_batch(h, rows));
+    RQ_TRY(ensure_batch(h, rows, fan ? rows / fan : 0));
     StepCtx c{};
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
+    c.fan = fan;
     c.guided = guided; c.Bs = batch; c.gscale = gscale; c.logp = arm.on();
     c.trunc = trunc; c.min_p = tr_mp.data(); c.typical_p = tr_typ.data();
     if (rp) {
@@ -1056,7 +1147,8 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             rqamd_rqt::SchedTables& t = h->sch_image;
             t.T = (float*)q; t.tk = (int*)(q + tb); t.tp = (float*)(q + 2 * tb); t.gs = (float*)(q + 3 * tb); t.mp = (float*)(q + 4 * tb); t.typ = (float*)(q + 5 * tb);
             h->sch_image_rows = (size_t)batch;
-            for (int f = rqamd_rqt::NFAM_SCHED0; f < rqamd_rqt::NFAM; ++f) if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = true;
+            for (int f = rqamd_rqt::NFAM_SCHED0; f < rqamd_rqt::NFAM; ++f)
+                if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = h->gstale[f + rqamd_rqt::NFAM] = true;
         }
         const rqamd_rqt::SchedTables& t = pi ? h->sch_image : h->sch_shared;
         RQ_HIP(hipMemcpyAsync(t.T, hT, nt * 4, hipMemcpyHostToDevice, st));
@@ -1073,14 +1165,14 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
     // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
     rqamd_rqt::Key k{};
-    k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream;
+    k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream; k.fan = fan;
     for (int d = 0; d < h->D; ++d) k.cb[d] = codebooks[d];
     if (!rp && !sarm.on()) {       // (per-row and scheduled calls: no parameter value is in a captured launch, so none is in the key)
         k.T = temperature; k.gs = guided ? gscale : 0.f;
         for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
         if (trunc) for (int d = 0; d < h->D; ++d) { k.mp[d] = tr_mp[d]; k.typ[d] = tr_typ[d]; }
     }
-    const int fam = step_family(c);
+    const int fam = graph_family(c);
     if (!h->gkey_set[fam] || memcmp(&k, &h->gkey[fam], sizeof(k)) != 0) { h->gstale[fam] = true; h->gkey[fam] = k; h->gkey_set[fam] = true; }
     RQ_LAUNCH(set_rng_kernel, dim3(1), dim3(64), 0, st, h->rng, seed, offset);
     h->prof.used = 0; h->prof.bytes = 0; h->prof.flops = 0; h->prof.used_attn = 0;
@@ -1211,6 +1303,22 @@ extern "C" int rqamd_rqt_sample_schedule(rqamd_rqt* h, const float* temperature,
     if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: null handle");
     h->sarm = rqamd_rqt::SchedArm{temperature, top_k, top_p, guidance_scale, min_p, typical_p, 0};
     h->sarm.per_image = h->sarm.on() && per_image ? 1 : 0;
+    return RQAMD_OK;
+}
+
+// Arms the next rqamd_rqt_sample / _masked / _guided / _rows call on the handle as a shared-prompt call (include/rqamd.h): `fan` rows per
+// group, one row of cond / uncond per group.  0 disarms.
+extern "C" int rqamd_rqt_sample_shared(rqamd_rqt* h, int fan) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_shared: null handle");
+    h->shared_fan = 0;
+    if (fan < 0) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_shared: fan = %d < 0", fan);
+    h->shared_fan = fan;
+    return RQAMD_OK;
+}
+
+extern "C" int rqamd_rqt_kv_bytes(rqamd_rqt* h, int64_t* bytes) {
+    if (!h || !bytes) return rq_fail(RQAMD_ERR_INVALID, "rqt_kv_bytes: null argument");
+    *bytes = (int64_t)(h->kv.bytes + h->kvg.bytes);
     return RQAMD_OK;
 }
 
@@ -1581,7 +1689,7 @@ extern "C" int rqamd_dbg_rqt_share_params(rqamd_rqt* dst, const rqamd_rqt* src) 
         for (size_t i = 0; i < d.size(); ++i) {
             RqtLayer keep = d[i];
             d[i] = s[i];
-            d[i].kc = keep.kc; d[i].vc = keep.vc; d[i].ksc = keep.ksc; d[i].vsc = keep.vsc;
+            d[i].kc = keep.kc; d[i].vc = keep.vc; d[i].ksc = keep.ksc; d[i].vsc = keep.vsc; d[i].kcs = keep.kcs; d[i].vcs = keep.vcs;
         }
     };
     cp(dst->body, src->body); cp(dst->head, src->head);

@@ -46,6 +46,23 @@ struct AttnDecodeArgs {
     int rows, nh, E, Tcap;
 };
 
+// Decode attention of a shared-prompt sampling call (rqt_attn_shared.hip): the `fan` consecutive rows of a group share one copy of the
+// conditioning prefix.  Global key j < Ps is row j of the group's cache, key j >= Ps is row j - Ps of the row's own cache; this token
+// (global index t >= Ps) is appended at own row t - Ps.  Head size 64, bf16 / fp16, Ps + Tcap <= 256.
+struct AttnSharedArgs {
+    const bf16_t* qkv;      // [rows][3E], as AttnDecodeArgs
+    const bf16_t* kcs;      // group K cache [rows / fan][nh][Ps][64], read only
+    const bf16_t* vcs;      // group V cache, likewise
+    bf16_t* kc;             // own K cache [rows][nh][Tcap][64]
+    bf16_t* vc;             // own V cache
+    bf16_t* y;              // [rows][E]
+    const int* step;        // device-side step counter (or null)
+    int step_off;           // t = *step + step_off = global index of this token's key
+    int t_max;              // host-side upper bound of t (selects the register-block count), -1 = Ps + Tcap - 1
+    int rows, fan, nh, E, Ps, Tcap;
+};
+int rq_launch_attn_shared(const AttnSharedArgs& a, hipStream_t s);
+
 // Multi-token prefill of the conditioning prefix (transformers.py:235-239 of the reference: the first cached body step
 // runs the whole prefix through MultiSelfAttention.forward with the causal mask, attentions.py:60-104).
 struct AttnPrefillArgs {

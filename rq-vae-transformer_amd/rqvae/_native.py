@@ -100,6 +100,8 @@ _SIGS = {
     'rqamd_rqt_sample_trunc': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     'rqamd_rqt_sample_schedule': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    'rqamd_rqt_sample_shared': (C.c_int, [C.c_void_p, C.c_int]),
+    'rqamd_rqt_kv_bytes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     'rqamd_rqt_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -135,11 +137,14 @@ _SIGS = {
     'rqamd_dbg_rqt_attn_prefill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_dbg_rqt_attn_packed': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_rqt_attn_shared': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
 
-EXPORTS_F16 = tuple(n for n in _SIGS if n.startswith('rqamd_rqt_') or n.startswith('rqamd_vae_')) + ('rqamd_abi_version', 'rqamd_last_error', 'rqamd_dbg_set_row_scale')
+EXPORTS_F16 = tuple(n for n in _SIGS if n.startswith('rqamd_rqt_') or n.startswith('rqamd_vae_')) + ('rqamd_abi_version', 'rqamd_last_error', 'rqamd_dbg_set_row_scale',
+                                                                                                           'rqamd_dbg_rqt_attn_decode', 'rqamd_dbg_rqt_attn_shared')
 
 
 def _bind(path, names=None):
@@ -620,15 +625,33 @@ def dbg_vae_attn(qkv, form=0, out=None):
     return out
 
 
-def dbg_rqt_attn_decode(qkv, kc, vc, y, nh, Tcap, t, t_max=-1, ksc=None, vsc=None, step=None, step_base=0):
+def dbg_rqt_attn_decode(qkv, kc, vc, y, nh, Tcap, t, t_max=-1, ksc=None, vsc=None, step=None, step_base=0, half=False):
     """diagnostics: one decode step of the RQ-Transformer's attention alone (include/rqamd.h: rqamd_dbg_rqt_attn_decode).  qkv (rows, 3E)
     bf16, y (rows, E) bf16, caches (rows, nh, Tcap, hd) bf16 -- or uint8 with fp32 scales ksc / vsc (rows, nh, Tcap); step: a one-element
-    int32 tensor through which t reaches the kernel (set to step_base first), or None."""
+    int32 tensor through which t reaches the kernel (set to step_base first), or None.  half: the fp16 build of the library, every 16-bit
+    tensor torch.float16."""
     rows, E3 = qkv.shape
+    L, dt = (lib16(), torch.float16) if half else (lib(), torch.bfloat16)
     with on_device_of(qkv):
-        check(lib().rqamd_dbg_rqt_attn_decode(ptr(qkv, torch.bfloat16), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
-                                              rows, int(nh), E3 // 3, int(Tcap), int(t), int(t_max), ptr(step, torch.int32), int(step_base),
-                                              ptr(y, torch.bfloat16), stream_of(qkv)))
+        check(L.rqamd_dbg_rqt_attn_decode(ptr(qkv, dt), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
+                                          rows, int(nh), E3 // 3, int(Tcap), int(t), int(t_max), ptr(step, torch.int32), int(step_base),
+                                          ptr(y, dt), stream_of(qkv)), L)
+    return y
+
+
+def dbg_rqt_attn_shared(qkv, kcs, vcs, kc, vc, y, fan, nh, t, t_max=-1, step=None, step_base=0, half=False):
+    """diagnostics: one decode step of the shared-prompt attention alone (include/rqamd.h: rqamd_dbg_rqt_attn_shared).  qkv (rows, 3E), y
+    (rows, E), the group caches kcs / vcs (rows / fan, nh, Ps, 64) and the own caches kc / vc (rows, nh, Tcap_row, 64), bf16 -- or, half,
+    torch.float16 through the fp16 build of the library; t: the global index of this token's key (Ps .. Ps + Tcap_row - 1); step as in
+    dbg_rqt_attn_decode."""
+    rows, E3 = qkv.shape
+    L, dt = (lib16(), torch.float16) if half else (lib(), torch.bfloat16)
+    Ps = int(kcs.shape[2]) if kcs is not None else 0
+    Tcap = int(kc.shape[2]) if kc is not None else 0
+    with on_device_of(qkv):
+        check(L.rqamd_dbg_rqt_attn_shared(ptr(qkv, dt), ptr(kcs, dt), ptr(vcs, dt), ptr(kc, dt), ptr(vc, dt), rows, int(fan), int(nh), E3 // 3,
+                                          Ps, Tcap, int(t), int(t_max), ptr(step, torch.int32), int(step_base), ptr(y, dt),
+                                          stream_of(qkv)), L)
     return y
 
 
@@ -777,8 +800,9 @@ class RqtEngine(_Engine):
         c = self.cfg
         if codes.dim() != 4 or tuple(codes.shape[1:]) != (c.H, c.W, c.D):
             raise ValueError(f'codes of shape {tuple(codes.shape)}; expected (B, {c.H}, {c.W}, {c.D})')
-        if cond is not None and tuple(cond.shape) != (codes.shape[0], max(c.block_size_cond, 1)):
-            raise ValueError(f'cond of shape {tuple(cond.shape)}; expected ({codes.shape[0]}, {max(c.block_size_cond, 1)})')
+        n_cond = self._cond_rows(codes.shape[0])
+        if cond is not None and tuple(cond.shape) != (n_cond, max(c.block_size_cond, 1)):
+            raise ValueError(f'cond of shape {tuple(cond.shape)}; expected ({n_cond}, {max(c.block_size_cond, 1)})')
         if len(codebooks) < c.D:
             raise ValueError(f'{len(codebooks)} codebooks for depth {c.D}')
         if c.input_emb_vqvae or c.head_emb_vqvae:
@@ -786,6 +810,27 @@ class RqtEngine(_Engine):
                 if cb.dim() != 2 or cb.shape[0] < c.vocab_sizes[d] or cb.shape[1] != c.input_embed_dim:
                     raise ValueError(f'codebook of shape {tuple(cb.shape)}; expected (>= {c.vocab_sizes[d]}, {c.input_embed_dim})')
         self._on_my_device(codes, cond, *codebooks[:c.D])
+
+    def arm_shared(self, fan):
+        """rqamd_rqt_sample_shared for the NEXT sample / sample_masked / sample_guided / sample_rows call of this object: a shared-prompt
+        call of `fan` rows per group -- `partial` has G * fan rows, `cond` / `uncond` G rows.  0 / None disarms."""
+        self._shared = int(fan) if fan else 0
+
+    def _cond_rows(self, B):
+        """rows of cond / uncond the next sampling call expects for B images"""
+        fan = getattr(self, '_shared', 0)
+        if not fan:
+            return B
+        if fan < 0 or B % fan:
+            self._shared = 0
+            raise ValueError(f'shared-prompt call: {B} images are not a multiple of the group size {fan}')
+        return B // fan
+
+    def kv_bytes(self):
+        """device bytes currently reserved for the KV caches of the handle (rqamd_rqt_kv_bytes)"""
+        n = C.c_int64()
+        check(self._L.rqamd_rqt_kv_bytes(self._h, C.byref(n)), self._L)
+        return n.value
 
     def arm_trunc(self, min_p, typical_p, per_image=False):
         """rqamd_rqt_sample_trunc for the NEXT sample / sample_masked / sample_guided / sample_rows call of this object: min-p and
@@ -811,6 +856,13 @@ class RqtEngine(_Engine):
         is passed on to rqamd_rqt_sample_trunc / rqamd_rqt_sample_schedule the same way, and consumed"""
         trunc, self._trunc = getattr(self, '_trunc', None), None
         sched, self._sched = getattr(self, '_sched', None), None
+        fan, self._shared = getattr(self, '_shared', 0), 0
+        if fan:
+            unshared = call
+
+            def call():
+                rc = self._L.rqamd_rqt_sample_shared(self._h, fan)
+                return rc if rc != 0 else unshared()
         if sched is not None:
             n = self.cfg.H * self.cfg.W * self.cfg.D * (partial.shape[0] if sched[1] else 1)
             sarrs, host = [], []                     # (host tensors: the arrays the library reads, alive until the call returns)
@@ -892,7 +944,7 @@ class RqtEngine(_Engine):
         `uncond`, None = zeros as for `cond`).  `keep` / `pos_active` as in sample_masked, or None: nothing kept."""
         self._check(partial, cond, codebooks)
         if uncond is not None:
-            want = (partial.shape[0], max(self.cfg.block_size_cond, 1))
+            want = (self._cond_rows(partial.shape[0]), max(self.cfg.block_size_cond, 1))
             if tuple(uncond.shape) != want:
                 raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {want}')
             self._on_my_device(uncond)
@@ -931,7 +983,7 @@ class RqtEngine(_Engine):
         c = self.cfg
         D = c.D
         if uncond is not None:
-            want = (B, max(c.block_size_cond, 1))
+            want = (self._cond_rows(B), max(c.block_size_cond, 1))
             if tuple(uncond.shape) != want:
                 raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {want}')
             self._on_my_device(uncond)

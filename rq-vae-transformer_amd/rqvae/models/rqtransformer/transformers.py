@@ -14,6 +14,7 @@ cross-check of its cache, transformers.py:352-356); ``is_tqdm`` / ``desc`` have 
 whole loop is one asynchronous C call) and ``fast`` is unused by the reference itself."""
 import contextlib
 import functools
+import inspect
 import math
 import os
 from collections import OrderedDict, namedtuple
@@ -59,6 +60,38 @@ def _truncation_keywords(fn):
         with self.truncation(min_p=min_p, typical_p=typical_p):
             return fn(self, *args, **kwargs)
     return with_truncation
+
+
+def _shared_prompt(fn):
+    """sample() / sample_guided() inside ``with self.shared_cond(n)``: the checks of the shared-prompt form, made before anything runs, and
+    the mark that makes _cond() / _sampling_eng() treat `cond` / `uncond` as one row per group for the duration of this call only."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def shared(self, *args, **kwargs):
+        n = self._shared_cond
+        if not n or self._shared_live:
+            return fn(self, *args, **kwargs)
+        a = sig.bind(self, *args, **kwargs)
+        a.apply_defaults()
+        a = a.arguments
+        if self.sampler == 'torch' or not a['cached']:
+            raise NotImplementedError("shared_cond() needs the engine's own sampling loop: sampler='torch' and cached=False have no shared-prompt form")
+        B = a['partial_sample'].shape[0]
+        if B % n:
+            raise ValueError(f'shared_cond({n}): partial_sample has {B} images, not a multiple of {n}')
+        for name in ('cond', 'uncond'):
+            c = a.get(name)
+            if c is not None and (c.shape[0] != B // n or c.numel() != (B // n) * self.block_size_cond):
+                raise ValueError(f'shared_cond({n}): {name} of shape {tuple(c.shape)}; expected {(B // n, self.block_size_cond)} (one row per group of {n} images)')
+        self._shared_live = n
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            self._shared_live = 0
+            for eng, _ in self._engines.values():
+                eng.arm_shared(0)                     # (a call refused before it reached the library leaves nothing armed)
+    return shared
 
 
 class RQTransformer(Stage2Model):
@@ -133,6 +166,8 @@ class RQTransformer(Stage2Model):
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
         self._truncation = (None, None)                  # (min_p, typical_p) of the sample() calls inside `with self.truncation(...)`
         self._schedule = None                            # {parameter: tensor} of the sample() calls inside `with self.schedule(...)`
+        self._shared_cond = 0                            # images per prompt of the sample() calls inside `with self.shared_cond(n)`
+        self._shared_live = 0                            # ... while such a call runs (_shared_prompt)
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -188,13 +223,21 @@ class RQTransformer(Stage2Model):
 
     def _sampling_eng(self, amp=False):
         """_eng(amp) with the engine's "prefix.one_pass" option following self.prefix_mode (touched only when it has to change: a
-        handle of a model that never leaves the default never sees the option)"""
+        handle of a model that never leaves the default never sees the option), and -- inside shared_cond(n) only -- armed for a
+        shared-prompt call (the call consumes the arming, and _shared_prompt disarms whatever a refused call left: outside the context
+        the engine is not touched)"""
         want = self._prefix_one_pass()
         eng = self._eng(amp)
         if getattr(eng, '_prefix_one_pass', False) != want:
             eng.set_option('prefix.one_pass', int(want))
             eng._prefix_one_pass = want
+        if self._shared_live:
+            eng.arm_shared(self._shared_live)           # the next sampling call of the engine is a shared-prompt call
         return eng
+
+    def _cond_rows(self, B):
+        """rows of cond / uncond for B images: B, or -- a call inside shared_cond(n) -- one per group"""
+        return B // self._shared_live if self._shared_live else B
 
     @staticmethod
     def _codebooks(model_aux):
@@ -223,7 +266,7 @@ class RQTransformer(Stage2Model):
     def _cond(self, cond, B, device):
         if cond is None:
             return None                                  # engine zero-fills (transformers.py:208-209)
-        return cond.reshape(B, self.block_size_cond).to(device=device, dtype=torch.long).contiguous()
+        return cond.reshape(self._cond_rows(B), self.block_size_cond).to(device=device, dtype=torch.long).contiguous()
 
     def _on_side_stream(self, device, fn):
         return self._side.run(device, fn)
@@ -390,6 +433,7 @@ class RQTransformer(Stage2Model):
         return model_aux.quantizer
 
     @_truncation_keywords
+    @_shared_prompt
     @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, keep_mask=None):
@@ -595,6 +639,30 @@ class RQTransformer(Stage2Model):
 
     # ------------------------------------------------------------------ per-image sampling parameters
     @contextlib.contextmanager
+    def shared_cond(self, n):
+        """Shared-prompt sampling (not in the reference's model; its notebooks repeat one tokenised prompt num_samples times): the
+        sample() / sample_guided() calls made inside the block draw ``n`` images per prompt.  ``partial_sample`` has G * n rows, ``cond``
+        (and ``uncond``) G rows; image r belongs to prompt r // n.  Image r is drawn exactly as the plain call with
+        ``cond.repeat_interleave(n, 0)`` draws it -- same kernels, filters, Philox key and counters -- but the text prefix of a prompt
+        goes through the body stack once, its keys and values are cached once, and the decode attention reads that one copy for the n
+        images (rqamd_rqt_sample_shared).  The codes equal the plain call's bit for bit wherever the prefill over G prompts and the
+        prefill over G * n rows fall into one GEMM regime, and differ only where a draw was close elsewhere, as with prefix_mode.
+        Text-conditioned models (block_size_cond >= 2) with body head size 64, a body context of at most 256 tokens and the default
+        cache format.  Composes with keep_mask, start_loc, seeds(), return_log_probs(), truncation(), schedule(), amp and per-image
+        tensors (B = G * n values); a code prefix is stepped whatever prefix_mode says.  ``sampler='torch'`` and ``cached=False`` raise
+        NotImplementedError, a ``cond`` / ``uncond`` of another shape ValueError.  n = 1 is allowed and runs the shared path.
+        The engine's KV workspace has one layout at a time: the first shared call after a plain one (and the other way round) lays
+        it out again and recaptures its graphs."""
+        n = int(n)
+        if n < 1:
+            raise ValueError(f'shared_cond({n}): n must be >= 1')
+        saved, self._shared_cond = self._shared_cond, n
+        try:
+            yield self
+        finally:
+            self._shared_cond = saved
+
+    @contextlib.contextmanager
     def seeds(self, seeds):
         """Per-image Philox seeds for the sample() / sample_guided() calls made inside the block: ``seeds`` is a (B,) integer tensor
         or a sequence of B non-negative integers.  Image b is then drawn from the stream of row 0 of a call made after
@@ -694,8 +762,8 @@ class RQTransformer(Stage2Model):
         (H, W, D) = self.block_size
         B = partial_sample.shape[0]
         device = partial_sample.device
-        if guided and uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
-            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+        if guided and uncond is not None and (uncond.shape[0] != self._cond_rows(B) or uncond.numel() != self._cond_rows(B) * self.block_size_cond):
+            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(self._cond_rows(B), self.block_size_cond)} (the shape of cond)')
         if rows['seeds'] is not None and self.sampler == 'torch':
             raise ValueError("sampler='torch' draws with torch.multinomial from the device generator, which has no per-row key: seeds() is "
                              'available with the default sampler')
@@ -740,6 +808,7 @@ class RQTransformer(Stage2Model):
         return self._with_log_probs(want_logp, self._on_side_stream(device, run))
 
     @_truncation_keywords
+    @_shared_prompt
     @torch.no_grad()
     def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                       amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, uncond=None, guidance_scale=1.0,
@@ -773,8 +842,8 @@ class RQTransformer(Stage2Model):
         top_k_list, top_p_list = self._filter_lists(top_k, top_p)
         B = partial_sample.shape[0]
         device = partial_sample.device
-        if uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
-            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+        if uncond is not None and (uncond.shape[0] != self._cond_rows(B) or uncond.numel() != self._cond_rows(B) * self.block_size_cond):
+            raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(self._cond_rows(B), self.block_size_cond)} (the shape of cond)')
         eng = self._sampling_eng(amp)
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
@@ -928,8 +997,8 @@ class RQTransformer(Stage2Model):
         rows = self._per_image(B, temperature, top_k, top_p, guidance_scale if guided else None, force=force_rows)
         top_k_list, top_p_list = (None, None) if rows is not None else self._filter_lists(top_k, top_p)
         if guided:
-            if uncond is not None and (uncond.shape[0] != B or uncond.numel() != B * self.block_size_cond):
-                raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(B, self.block_size_cond)} (the shape of cond)')
+            if uncond is not None and (uncond.shape[0] != self._cond_rows(B) or uncond.numel() != self._cond_rows(B) * self.block_size_cond):
+                raise ValueError(f'uncond of shape {tuple(uncond.shape)}; expected {(self._cond_rows(B), self.block_size_cond)} (the shape of cond)')
             if rows is None and not math.isfinite(float(guidance_scale)):
                 raise ValueError(f'guidance_scale {guidance_scale} is not finite')
         eng = self._sampling_eng(amp)
