@@ -288,6 +288,38 @@ int rqamd_rqt_sample_guided(rqamd_rqt* h, const int64_t* partial, const uint8_t*
  * (rows, vocab) fp32, contiguous, device memory; vocab >= 1 (16-byte accesses when vocab % 4 == 0 and the three bases are aligned).
  * For host-driven loops (rqamd_rqt_step_logits over 2 * batch rows) and for tests; the engine never materialises g. */
 int rqamd_guide_logits(const float* cond_logits, const float* uncond_logits, int rows, int vocab, float scale, float* out, void* stream);
+/* Composed guidance: negative prompts and extra conditions inside the engine (not in the reference); additive, ABI v7.  Arms the NEXT
+ * rqamd_rqt_sample_guided call, or guided rqamd_rqt_sample_rows call, on the handle; that call consumes the arming whether it
+ * succeeds or fails.  n_extra = 0 disarms.  extra_cond: n_extra DEVICE pointers to (batch, block_size_cond) int64 each, a NULL entry
+ * (or a NULL array) = zeros as for cond; the pointer array is copied when the call arms, the conditionings are read by the armed call.
+ * extra_weight: HOST array of n_extra * batch finite values, condition-major (weight of condition k for image b at [k * batch + b]),
+ * read by the armed call.  The `batch` images then run as (2 + n_extra) * batch rows: row b under cond[b], row batch + b under uncond[b],
+ * row (2 + k) * batch + b under extra_cond[k][b], all started from the same `partial` and `keep`.  With c, u and x_k the raw logits of
+ * those rows and w_k = extra_weight[k * batch + b], every code of image b is drawn from
+ *     G = u + s (c - u) + sum_k w_k (x_k - u)
+ * -- a negative prompt is an extra condition with w < 0, a second prompt one with w > 0 -- computed in fp32 as
+ *     e = 0;  for k = 0 .. n_extra - 1:  e = fmaf(w_k, x_k - u, e)
+ *     (c == -inf || e == 0) ?  c' = c, u' = u  :  c' = c + e, u' = u + e;        g = guide(c', u', s)
+ * with guide() of rqamd_rqt_sample_guided.  Columns LogitMask holds at -inf in every row stay -inf (never inf - inf); e == 0 -- every
+ * weight zero, or every extra row equal to the unconditional one -- leaves the pair untouched bit for bit, so such a call draws what
+ * the guided call over the same (2 + n_extra) * batch rows would.  The fold is one launch per head step (csrc/rqt_compose.hip) into a
+ * scratch of the handle; the sampler kernels, filters, temperature and Philox counters are those of the guided call, and the code is
+ * written to all 2 + n_extra rows of the image.  It composes with rqamd_rqt_sample_logp (draw: under the composed distribution;
+ * model / model_uncond: the raw logits of rows b and batch + b, as without extra conditions), _trunc and _schedule (a guidance
+ * schedule applies to s alone; the weights have no schedule), keep, start_h / start_w and "prefix.one_pass".
+ * Composed calls replay graph sets of their own, keyed on the rows and n_extra next to the fields of the family the call would
+ * otherwise belong to; the weights live in a device table and are in no key: alternating composed, guided and plain calls recaptures
+ * nothing, new weights recapture nothing, another n_extra recaptures the composed sets only.
+ * Refused before anything is enqueued, RQAMD_ERR_INVALID: n_extra outside 0 .. RQAMD_RQT_MAX_EXTRA_CONDS (by this call), a NaN or
+ * infinite weight, an arming in front of an unguided call; RQAMD_ERR_UNSUPPORTED: an arming together with rqamd_rqt_sample_shared. */
+#define RQAMD_RQT_MAX_EXTRA_CONDS 4
+int rqamd_rqt_sample_compose(rqamd_rqt* h, int n_extra, const int64_t* const* extra_cond, const float* extra_weight);
+/* out[r][v] = guide(c', u', scale) of rqamd_rqt_sample_compose, through the same device function: cond_logits, uncond_logits, out
+ * (rows, vocab) fp32, extra_logits (n_extra, rows, vocab) fp32, extra_weight (n_extra, rows) fp32, all contiguous DEVICE memory;
+ * 1 <= n_extra <= RQAMD_RQT_MAX_EXTRA_CONDS, vocab >= 1 (16-byte accesses when vocab % 4 == 0 and the bases are aligned).  For
+ * host-driven loops over (2 + n_extra) * batch rows and for tests; the engine folds into its own scratch and never calls it. */
+int rqamd_compose_logits(const float* cond_logits, const float* uncond_logits, const float* extra_logits, int n_extra,
+                         const float* extra_weight, int rows, int vocab, float scale, float* out, void* stream);
 /* Sampling parameters per image (not in the reference); additive, ABI v7.  One entry point for plain, masked and guided sampling:
  * keep NULL: unmasked (pos_active_host is ignored), else as in rqamd_rqt_sample_masked; uncond NULL and guidance_scale NULL: unguided,
  * else as in rqamd_rqt_sample_guided (uncond NULL = zeros; uncond without guidance_scale is RQAMD_ERR_INVALID).

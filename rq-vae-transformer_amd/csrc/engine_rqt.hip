@@ -120,6 +120,15 @@ struct rqamd_rqt {
     int cur_fan = 0;       // rows per group of the shared-prompt call being run (the body stack's attention launches read it)
     int kv_groups = 0;
     DevBuf kvg;
+    // composed guidance (rqamd_rqt_sample_compose): the arming -- the extra conditionings (device pointers, copied when the call arms) and
+    // the HOST weights (n * batch, read by the next sampling call) -- and what the fold launches of such a call use: a scratch of 2 B V
+    // floats (c', u': rqt_compose.hip) and the device weight table (K, B), memory of their own, allocated by the first composed call
+    // outside any capture and kept; they grow with the batch, which drops the composed graphs that hold their addresses
+    struct ComposeArm { int n; const int64_t* cond[RQ_MAX_EXTRA_CONDS]; const float* weight; } carm = {};
+    DevBuf cmp_buf;
+    float *cmp_logits = nullptr, *cmp_w = nullptr;
+    size_t cmp_rows = 0;            // images the two hold
+    std::vector<float> cmp_host;    // host staging of the weight table, like row_host
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -152,9 +161,11 @@ struct rqamd_rqt {
     static constexpr int NFAM = 56;
     // Shared-prompt calls (rqamd_rqt_sample_shared: another attention launch in the body stack, other cache addresses) are every family
     // once more, keys NFAM .. 2 * NFAM - 1 and sets 2 * NFAM .. 4 * NFAM - 1 (graph_family); the group size is part of their key.
-    hipGraphExec_t gexec[4 * NFAM][NGRAPH] = {};
-    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; int fan; int fan_pad; } gkey[2 * NFAM];
-    bool gkey_set[2 * NFAM] = {}, gstale[2 * NFAM] = {};
+    // Composed calls (rqamd_rqt_sample_compose: (2 + K) B rows, a fold launch per head step, the sampler reads the scratch) are every family
+    // a third time, keys 2 * NFAM .. 3 * NFAM - 1 and sets 4 * NFAM .. 6 * NFAM - 1; K is part of their key next to the rows, no weight is.
+    hipGraphExec_t gexec[6 * NFAM][NGRAPH] = {};
+    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; int fan; int n_extra; } gkey[3 * NFAM];
+    bool gkey_set[3 * NFAM] = {}, gstale[3 * NFAM] = {};
     bool gvalid = false;
     int64_t n_capture = 0;     // position graphs captured over the life of the handle (rqamd_rqt_graph_captures)
 
@@ -686,6 +697,8 @@ struct StepCtx {
     const float* typical_p; //  calls read h->row_mp / h->row_typ at every depth
     bool sched;            // scheduled call (rqamd_rqt_sample_schedule): the scheduled per-row samplers read EVERY parameter at (row, position, depth) from
     bool sched_per_image;  //   h->sch_image (a schedule per image) or h->sch_shared (one for all rows); trunc: the min-p / typical tables are read too
+    int n_extra;           // composed call (rqamd_rqt_sample_compose): K extra row blocks behind the twins, B = (2 + K) * Bs rows; 0: none
+    const int64_t* const* extra_cond;   //   their conditionings (Bs rows each, null entries: zeros)
     int fan;               // shared-prompt call (rqamd_rqt_sample_shared): rows per group, `cond` / `uncond` hold B / fan (guided: Bs / fan) rows; 0: a plain call
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
@@ -779,6 +792,15 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
         s.redo = h->smp_redo; s.rng = h->rng; s.pos = h->st; s.d = d; s.D = h->D; s.out = h->xs; s.out_stride = (long)h->HW * h->D;
         s.keep = c.keep; s.keep_stride = s.out_stride;
         if (c.guided) { s.rows = c.Bs; s.logits_u = h->logits + (long)c.Bs * h->V; s.gscale = c.gscale; s.out_mirror = (long)c.Bs * s.out_stride; }
+        if (c.n_extra) {
+            // composed guidance: the K extra blocks are folded into the pair (c', u' -> the scratch; h->logits stays raw for the step's
+            // log_prob launch), the sampler reads the pair from there and writes the code to all K + 2 rows of the image
+            ComposeArgs f{};
+            f.c = h->logits; f.u = s.logits_u; f.x = h->logits + 2 * (long)c.Bs * h->V; f.w = h->cmp_w; f.rows = c.Bs; f.V = h->V; f.K = c.n_extra;
+            f.out_c = h->cmp_logits; f.out_u = h->cmp_logits + (long)c.Bs * h->V; f.scale = 1.f;
+            RQ_TRY(rq_launch_compose(f, st));
+            s.logits = f.out_c; s.logits_u = f.out_u; s.out_mirror_n = c.n_extra;
+        }
         if (c.sched) {         // every value from the tables of the schedule, at (row, *st, d); the scalars are unused
             const rqamd_rqt::SchedTables& t = c.sched_per_image ? h->sch_image : h->sch_shared;
             s.temperature = 1.f; s.top_k = 0; s.top_p = -1.f;
@@ -823,7 +845,8 @@ static int step_family(const StepCtx& c) {
 }
 
 // the key / graph-set family of a call: shared-prompt calls have every family of step_family once more
-static int graph_family(const StepCtx& c) { return step_family(c) + (c.fan ? rqamd_rqt::NFAM : 0); }
+// (and composed calls a third time; a call is never both)
+static int graph_family(const StepCtx& c) { return step_family(c) + (c.fan ? rqamd_rqt::NFAM : c.n_extra ? 2 * rqamd_rqt::NFAM : 0); }
 
 // everything that happens at one spatial position (position read from h->st[0] on the device)
 static int position_sequence(rqamd_rqt* h, const StepCtx& c, bool first_pos, bool do_head, int host_pos, hipStream_t st) {
@@ -887,6 +910,12 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
         RQ_HIP(hipMemcpyAsync(h->xs + (size_t)n_in * h->HW * h->D, partial, xb, hipMemcpyDeviceToDevice, st));
         if (uncond) RQ_HIP(hipMemcpyAsync(h->cond + (size_t)n_in * h->cond_len, uncond, cb, hipMemcpyDeviceToDevice, st));
         else RQ_HIP(hipMemsetAsync(h->cond + (size_t)n_in * h->cond_len, 0, cb, st));
+        for (int k = 0; k < c.n_extra; ++k) {      // composed call: block 2 + k starts from the same codes, under the k-th extra conditioning
+            RQ_HIP(hipMemcpyAsync(h->xs + (size_t)(2 + k) * n_in * h->HW * h->D, partial, xb, hipMemcpyDeviceToDevice, st));
+            int64_t* dst = h->cond + (size_t)(2 + k) * n_in * h->cond_len;
+            if (c.extra_cond[k]) RQ_HIP(hipMemcpyAsync(dst, c.extra_cond[k], cb, hipMemcpyDeviceToDevice, st));
+            else RQ_HIP(hipMemsetAsync(dst, 0, cb, st));
+        }
     }
     RQ_TRY(rq_launch_set_int(h->st, 0, st));
     // Conditioning prefix (text tokens): tokens 0..cond_len-2 only fill the body KV cache (transformers.py:235-239; in
@@ -937,7 +966,8 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
     if (keep) {
         const size_t kb = (size_t)n_in * h->HW * h->D;
         RQ_HIP(hipMemcpyAsync(h->keep, keep, kb, hipMemcpyDeviceToDevice, st));
-        if (c.guided) RQ_HIP(hipMemcpyAsync(h->keep + kb, keep, kb, hipMemcpyDeviceToDevice, st));   // (the sampler reads rows 0..Bs-1)
+        if (c.guided)                                                                              // (the sampler reads rows 0..Bs-1)
+            for (int j = 1; j < 2 + c.n_extra; ++j) RQ_HIP(hipMemcpyAsync(h->keep + (size_t)j * kb, keep, kb, hipMemcpyDeviceToDevice, st));
         c.keep = h->keep;
     }
     if (n0 >= 1 && n0 < n_pos) RQ_TRY(prefix_prefill(h, c.codebooks, c.B, n0, st));      // (n0 == n_pos: no position draws, nothing runs)
@@ -1015,7 +1045,7 @@ static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
 }
 struct ArmGuard {          // an entry point that returns before sample_impl still consumes the armings
     rqamd_rqt* h;
-    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; h->shared_fan = 0; } }
+    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; h->shared_fan = 0; h->carm = {}; } }
 };
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
@@ -1033,6 +1063,18 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     h->sarm = {};
     const int fan = h->shared_fan;
     h->shared_fan = 0;
+    const rqamd_rqt::ComposeArm carm = h->carm;
+    h->carm = {};
+    const int K = carm.n;
+    if (K) {               // a composed call (rqamd_rqt_sample_compose): refused here, before anything is enqueued
+        if (!guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: extra conditions armed in front of an unguided call");
+        if (fan) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_compose: extra conditions together with rqamd_rqt_sample_shared (no group caches for the extra blocks)");
+        if (K < 0 || K > RQ_MAX_EXTRA_CONDS) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: %d extra conditions (at most %d)", K, (int)RQ_MAX_EXTRA_CONDS);
+        if (!carm.weight) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: null weights");
+        if (batch > 0x7fffffff / (2 + K)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: (2 + %d) * batch overflows", K);
+        for (long i = 0; i < (long)K * batch; ++i)
+            if (!(carm.weight[i] - carm.weight[i] == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: weight[%ld] must be finite", i);
+    }
     if (fan) {             // a shared-prompt call (rqamd_rqt_sample_shared): refused here, before anything is enqueued
         if (fan < 0 || batch % fan) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_shared: batch %d is not a multiple of the group size %d", batch, fan);
         if (h->cfg.block_size_cond < 2) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_shared: block_size_cond = %d: no text prefix to share", h->cfg.block_size_cond);
@@ -1075,9 +1117,25 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             if (sarm.typical_p && !(sarm.typical_p[i] - sarm.typical_p[i] == 0.f)) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_schedule: typical_p[%zu] must be finite", i);
         }
     }
-    const int rows = guided ? 2 * batch : batch;
+    const int rows = guided ? (2 + K) * batch : batch;
     RQ_TRY(ensure_batch(h, rows, fan ? rows / fan : 0));
     StepCtx c{};
+    c.n_extra = K; c.extra_cond = carm.cond;
+    if (K) {
+        // the fold's scratch and weight table: first use, or a larger batch, outside any capture -- the composed graphs hold the old addresses.
+        // Weights: host array -> staging block of the handle -> device table by an asynchronous copy ahead of the position loop (see row_host)
+        if ((size_t)batch > h->cmp_rows) {
+            h->cmp_rows = 0;
+            const size_t lb = al(2 * (size_t)batch * h->V * 4);
+            RQ_TRY(h->cmp_buf.reserve(lb + al((size_t)RQ_MAX_EXTRA_CONDS * batch * 4)));
+            h->cmp_logits = (float*)h->cmp_buf.p; h->cmp_w = (float*)((char*)h->cmp_buf.p + lb);
+            h->cmp_rows = (size_t)batch;
+            for (int f = 2 * rqamd_rqt::NFAM; f < 3 * rqamd_rqt::NFAM; ++f) h->gstale[f] = true;
+        }
+        RQ_HIP(hipStreamSynchronize(st));
+        h->cmp_host.assign(carm.weight, carm.weight + (size_t)K * batch);
+        RQ_HIP(hipMemcpyAsync(h->cmp_w, h->cmp_host.data(), (size_t)K * batch * 4, hipMemcpyHostToDevice, st));
+    }
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
     c.fan = fan;
     c.guided = guided; c.Bs = batch; c.gscale = gscale; c.logp = arm.on();
@@ -1148,7 +1206,7 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             t.T = (float*)q; t.tk = (int*)(q + tb); t.tp = (float*)(q + 2 * tb); t.gs = (float*)(q + 3 * tb); t.mp = (float*)(q + 4 * tb); t.typ = (float*)(q + 5 * tb);
             h->sch_image_rows = (size_t)batch;
             for (int f = rqamd_rqt::NFAM_SCHED0; f < rqamd_rqt::NFAM; ++f)
-                if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = h->gstale[f + rqamd_rqt::NFAM] = true;
+                if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = h->gstale[f + rqamd_rqt::NFAM] = h->gstale[f + 2 * rqamd_rqt::NFAM] = true;
         }
         const rqamd_rqt::SchedTables& t = pi ? h->sch_image : h->sch_shared;
         RQ_HIP(hipMemcpyAsync(t.T, hT, nt * 4, hipMemcpyHostToDevice, st));
@@ -1165,7 +1223,7 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     // graph cache key: anything baked into kernel arguments (the keep-flag pointer is not in it: masked calls have a graph set of their
     // own).  One key per family: a guided call never invalidates the unguided graphs, nor the other way round
     rqamd_rqt::Key k{};
-    k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream; k.fan = fan;
+    k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream; k.fan = fan; k.n_extra = K;
     for (int d = 0; d < h->D; ++d) k.cb[d] = codebooks[d];
     if (!rp && !sarm.on()) {       // (per-row and scheduled calls: no parameter value is in a captured launch, so none is in the key)
         k.T = temperature; k.gs = guided ? gscale : 0.f;
@@ -1313,6 +1371,22 @@ extern "C" int rqamd_rqt_sample_shared(rqamd_rqt* h, int fan) {
     h->shared_fan = 0;
     if (fan < 0) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_shared: fan = %d < 0", fan);
     h->shared_fan = fan;
+    return RQAMD_OK;
+}
+
+// Arms the next rqamd_rqt_sample_guided call, or guided rqamd_rqt_sample_rows call, on the handle with extra conditions (include/rqamd.h):
+// n_extra device pointers (batch rows of conditioning each, null entries: zeros; the pointer ARRAY is copied here) and HOST weights
+// (n_extra * batch, condition-major), read and checked by that call.  0 disarms.
+extern "C" int rqamd_rqt_sample_compose(rqamd_rqt* h, int n_extra, const int64_t* const* extra_cond, const float* extra_weight) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: null handle");
+    h->carm = {};
+    if (n_extra == 0) return RQAMD_OK;
+    if (n_extra < 0 || n_extra > RQ_MAX_EXTRA_CONDS)
+        return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: %d extra conditions (0 .. RQAMD_RQT_MAX_EXTRA_CONDS = %d)", n_extra, (int)RQ_MAX_EXTRA_CONDS);
+    if (!extra_weight) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: null weights");
+    h->carm.n = n_extra;
+    for (int k = 0; k < n_extra; ++k) h->carm.cond[k] = extra_cond ? extra_cond[k] : nullptr;
+    h->carm.weight = extra_weight;
     return RQAMD_OK;
 }
 

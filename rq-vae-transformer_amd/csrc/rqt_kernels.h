@@ -135,8 +135,54 @@ struct SampleArgs {
     // at [row * row_stride + *pos * D + d]: row_stride = HW * D for a schedule per image, 0 for one shared by all rows.  `pos` is
     // required.  Row r at (pos, d) is drawn exactly as the per-row kernels draw it with the values the tables hold there.
     int sched = 0;
+    // composed guidance (rqamd_rqt_sample_compose: K extra row blocks behind the twins): the drawn code also goes to
+    // out[(row * out_stride + slot) + j * out_mirror] for j = 2 .. 1 + out_mirror_n.  0: the one twin of out_mirror alone, as before
+    int out_mirror_n = 0;
     long row_stride = 0;
 };
+
+// Classifier-free guidance: the logit a guided row is drawn from, u + s (c - u) written as c + (s - 1)(c - u) so that s = 1 returns c
+// bit for bit; a masked column (LogitMask: -inf in both rows) stays -inf instead of becoming inf - inf.  Raw logits, before the
+// temperature.  THE one place logits are mixed: the three samplers call it where they load their row, guide_logits_kernel for the
+// host paths.
+static __device__ __forceinline__ float guide_logit(float c, float u, float s) {
+    return c == -__int_as_float(0x7f800000) ? c : fmaf(s - 1.0f, c - u, c);
+}
+
+// Composed guidance (rqamd_rqt_sample_compose, rqamd_compose_logits): K <= RQ_MAX_EXTRA_CONDS extra conditionings with raw logits x_k and
+// weights w_k next to the pair (c, u).  The target is G = u + s (c - u) + sum_k w_k (x_k - u).  The extra term is folded into BOTH rows of
+// the pair, in fp32 and in this order,
+//     e = 0;  for k = 0 .. K-1:  e = fmaf(w_k, x_k - u, e)
+//     (c == -inf || e == 0) ?  c' = c, u' = u  :  c' = c + e, u' = u + e
+// and the samplers then draw from guide_logit(c', u', s) as they draw any guided pair: c' - u' is c - u up to rounding, so that is G.
+// Two rules are part of the contract.  c == -inf: LogitMask leaves -inf in the same columns of every row, x_k - u is inf - inf there and
+// e is NaN -- the pair stays as it is and guide_logit returns -inf.  e == 0 (every weight zero, every extra row equal to u): the pair
+// stays bit for bit -- c + 0.0f would turn a -0.0 logit into +0.0, which the samplers' order keys tell apart.
+// THE one place extra conditions enter: the fold kernel of the engine and rqamd_compose_logits call it (rqt_compose.hip).
+enum { RQ_MAX_EXTRA_CONDS = 4 };
+static __device__ __forceinline__ void compose_pair(float c, float u, const float (&x)[RQ_MAX_EXTRA_CONDS], const float (&w)[RQ_MAX_EXTRA_CONDS],
+                                                    int K, float& c_out, float& u_out) {
+    float e = 0.f;
+#pragma unroll
+    for (int k = 0; k < RQ_MAX_EXTRA_CONDS; ++k)
+        if (k < K) e = fmaf(w[k], x[k] - u, e);
+    const bool same = c == -__int_as_float(0x7f800000) || e == 0.f;
+    c_out = same ? c : c + e;
+    u_out = same ? u : u + e;
+}
+
+// The fold of composed guidance (rqt_compose.hip).  Row r of the pair: c[r], u[r]; extra k: x[(k * rows + r)][:]; weights w[k * rows + r].
+// out_u non-null (the engine's fold): c' -> out_c[r], u' -> out_u[r].  out_u null (rqamd_compose_logits): guide_logit(c', u', scale) -> out_c[r].
+struct ComposeArgs {
+    const float *c, *u;     // [rows][V] each
+    const float* x;         // [K][rows][V]
+    const float* w;         // [K][rows], device
+    int rows, V, K;
+    float* out_c;           // [rows][V]
+    float* out_u;           // [rows][V] or null
+    float scale;
+};
+int rq_launch_compose(const ComposeArgs& a, hipStream_t s);
 int rq_launch_sample_sched(const SampleArgs& a, hipStream_t s);     // rqt_sample_sched.hip
 // is a filter of the TRUNC instantiations in effect (scalars), or could one be (tables)?
 static inline bool rq_sample_trunc_on(const SampleArgs& a) {

@@ -1448,13 +1448,7 @@ static __device__ __forceinline__ bool sample_kept(const SampleArgs& p, int row)
     return p.keep && p.keep[(long)row * p.keep_stride + (p.pos ? (*p.pos) * p.D + p.d : 0)] != 0;
 }
 
-// Classifier-free guidance: the logit a guided row is drawn from, u + s (c - u) written as c + (s - 1)(c - u) so that s = 1 returns c
-// bit for bit; a masked column (LogitMask: -inf in both rows) stays -inf instead of becoming inf - inf.  Raw logits, before the
-// temperature.  THE one place logits are mixed: the three samplers call it where they load their row, guide_logits_kernel for the
-// host paths.
-static __device__ __forceinline__ float guide_logit(float c, float u, float s) {
-    return c == -__int_as_float(0x7f800000) ? c : fmaf(s - 1.0f, c - u, c);
-}
+// guide_logit(c, u, s), the one place the logits of a guided pair are mixed, is in rqt_kernels.h next to compose_pair (composed guidance).
 
 // Per-row parameters (ROWS = true, rqt_sample_rows.hip): the launcher runs the three kernels over all rows, and a workgroup goes on
 // only if its row's class is the kernel's own -- the choice launch_sample makes from the scalars, made per row from the row's values:
@@ -1530,12 +1524,15 @@ static __device__ __forceinline__ void sample_sched_params(SampleArgs& p, int ro
 
 // The three samplers are templates on GUIDED.  <false>: the unguided kernels, whose instruction stream the parameter leaves as it was.
 // <true>: the row of p.logits_u is loaded next to the row of p.logits, the same way, and the two are mixed through guide_logit();
-// the drawn code also goes to the twin's slot (p.out_mirror).
+// the drawn code also goes to the twin's slot (p.out_mirror) and to those of the extra blocks of a composed call (p.out_mirror_n).
 template <bool GUIDED>
 static __device__ __forceinline__ void sample_store(const SampleArgs& p, int row, int slot, int code) {
     const long o = (long)row * p.out_stride + slot;
     p.out[o] = (int64_t)code;
-    if (GUIDED && p.out_mirror) p.out[o + p.out_mirror] = (int64_t)code;
+    if (GUIDED && p.out_mirror) {
+        p.out[o + p.out_mirror] = (int64_t)code;
+        for (int j = 2; j <= 1 + p.out_mirror_n; ++j) p.out[o + j * p.out_mirror] = (int64_t)code;      // the extra blocks of a composed call
+    }
 }
 
 // TRUNC (rqt_sample_trunc.hip): min-p, then locally typical sampling, on the renormalised probabilities q that top-p leaves.

@@ -101,6 +101,8 @@ _SIGS = {
     'rqamd_rqt_sample_schedule': (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     'rqamd_rqt_sample_shared': (C.c_int, [C.c_void_p, C.c_int]),
+    'rqamd_rqt_sample_compose': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_compose_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_kv_bytes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
@@ -504,6 +506,31 @@ def guide_logits(c, u, scale):
     return out
 
 
+MAX_EXTRA_CONDS = 4            # RQAMD_RQT_MAX_EXTRA_CONDS
+
+
+def compose_logits(c, u, extras, weights, scale):
+    """rqamd_compose_logits: composed guidance on raw logits, guide(c', u', scale) with the K extra rows folded into the pair first (the
+    device function the engine's fold applies; include/rqamd.h: rqamd_rqt_sample_compose).  c, u (rows, vocab) fp32; extras (K, rows,
+    vocab) fp32; weights (K, rows) fp32, all on one device, 1 <= K <= MAX_EXTRA_CONDS -> (rows, vocab) fp32."""
+    if c.dim() != 2 or tuple(u.shape) != tuple(c.shape):
+        raise ValueError(f'compose_logits: logits of shapes {tuple(c.shape)} and {tuple(u.shape)}; expected two equal (rows, vocab)')
+    rows, vocab = c.shape
+    if extras.dim() != 3 or tuple(extras.shape[1:]) != (rows, vocab) or not 1 <= extras.shape[0] <= MAX_EXTRA_CONDS:
+        raise ValueError(f'compose_logits: extra logits of shape {tuple(extras.shape)}; expected (1 .. {MAX_EXTRA_CONDS}, {rows}, {vocab})')
+    K = extras.shape[0]
+    if tuple(weights.shape) != (K, rows):
+        raise ValueError(f'compose_logits: weights of shape {tuple(weights.shape)}; expected ({K}, {rows})')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'compose_logits: scale {scale} is not finite')
+    out = torch.empty_like(c)
+    c, u, extras, weights = (t.contiguous() for t in (c, u, extras, weights))
+    with on_device_of(c):
+        check(lib().rqamd_compose_logits(ptr(c, torch.float32), ptr(u, torch.float32), ptr(extras, torch.float32), K, ptr(weights, torch.float32),
+                                         rows, vocab, float(scale), ptr(out), stream_of(c)))
+    return out
+
+
 def dbg_gemm(a_bf16, w_bf16, bias=None, epi=3, bm=0, bn=0, splitk=0, out=None):
     """diagnostics: out[M,N] = a[M,K] @ w[N,K]^T (+bias); a, w are torch.bfloat16."""
     M, K = a_bf16.shape
@@ -826,6 +853,35 @@ class RqtEngine(_Engine):
             raise ValueError(f'shared-prompt call: {B} images are not a multiple of the group size {fan}')
         return B // fan
 
+    def arm_compose(self, conds=None, weights=None):
+        """rqamd_rqt_sample_compose for the NEXT sample_guided / guided sample_rows call of this object: composed guidance.  `conds`: K
+        tensors (B, block_size_cond) int64 on the engine's device, or None entries (zeros); `weights`: K * B finite floats on the host,
+        condition-major.  None / an empty list disarms.  Checked when the call is made, before the library is called."""
+        self._compose = (list(conds), [float(w) for w in weights]) if conds else None
+
+    def _compose_arrays(self, B):
+        """the arming of arm_compose as the arguments of rqamd_rqt_sample_compose, checked (ValueError), and consumed"""
+        comp, self._compose = getattr(self, '_compose', None), None
+        if comp is None:
+            return None
+        conds, w = comp
+        K = len(conds)
+        if K > MAX_EXTRA_CONDS:
+            raise ValueError(f'{K} extra conditions; at most {MAX_EXTRA_CONDS}')
+        if len(w) != K * B:
+            raise ValueError(f'{len(w)} weights for {K} extra conditions of {B} images; expected {K * B}')
+        if not all(math.isfinite(x) for x in w):
+            raise ValueError('extra-condition weights must be finite')
+        want = (B, max(self.cfg.block_size_cond, 1))
+        for t in conds:
+            if t is not None and tuple(t.shape) != want:
+                raise ValueError(f'extra cond of shape {tuple(t.shape)}; expected {want}')
+        self._on_my_device(*conds)
+        parr = (C.c_void_p * K)()
+        for i, t in enumerate(conds):
+            parr[i] = None if t is None else ptr(t, torch.int64).value
+        return K, parr, (C.c_float * (K * B))(*w), conds
+
     def kv_bytes(self):
         """device bytes currently reserved for the KV caches of the handle (rqamd_rqt_kv_bytes)"""
         n = C.c_int64()
@@ -857,6 +913,19 @@ class RqtEngine(_Engine):
         trunc, self._trunc = getattr(self, '_trunc', None), None
         sched, self._sched = getattr(self, '_sched', None), None
         fan, self._shared = getattr(self, '_shared', 0), 0
+        try:
+            comp = self._compose_arrays(partial.shape[0])
+        except Exception:
+            self._trunc = self._sched = None
+            raise
+        if comp is not None:
+            if not guided:
+                raise ValueError('extra conditions armed in front of an unguided call')
+            uncomposed = call
+
+            def call(comp=comp):                     # (comp: the arrays and tensors the library reads, alive until the call returns)
+                rc = self._L.rqamd_rqt_sample_compose(self._h, comp[0], comp[1], comp[2])
+                return rc if rc != 0 else uncomposed()
         if fan:
             unshared = call
 

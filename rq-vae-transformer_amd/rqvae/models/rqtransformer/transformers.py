@@ -94,6 +94,27 @@ def _shared_prompt(fn):
     return shared
 
 
+def _negative_prompt(fn):
+    """sample_guided() also takes ``negative=`` / ``negative_scale=`` as keywords: the call then runs inside
+    ``self.extra_conds(conds=[negative], weights=[-negative_scale])`` (see extra_conds()); both the keyword and the context: ValueError.
+    The checks of composed guidance that need no tensor are made here, before anything runs.  (A wrapper, as _truncation_keywords is.)"""
+    @functools.wraps(fn)
+    def with_negative(self, *args, negative=None, negative_scale=1.0, **kwargs):
+        if negative is not None:
+            if self._extra_conds is not None:
+                raise ValueError('negative= given inside extra_conds(): pass the negative prompt as one of the extra conditions')
+            w = negative_scale if torch.is_tensor(negative_scale) else float(negative_scale)
+            with self.extra_conds(conds=[negative], weights=[-w]):
+                return with_negative(self, *args, **kwargs)
+        if self._extra_conds is not None:
+            if self.sampler == 'torch':
+                raise NotImplementedError("extra_conds() runs in the on-device sampler; sampler='torch' has no composed form")
+            if self._shared_cond:
+                raise NotImplementedError('extra_conds() inside shared_cond(): the extra row blocks would need group caches of their own')
+        return fn(self, *args, **kwargs)
+    return with_negative
+
+
 class RQTransformer(Stage2Model):
 
     def __init__(self, config):
@@ -168,6 +189,7 @@ class RQTransformer(Stage2Model):
         self._schedule = None                            # {parameter: tensor} of the sample() calls inside `with self.schedule(...)`
         self._shared_cond = 0                            # images per prompt of the sample() calls inside `with self.shared_cond(n)`
         self._shared_live = 0                            # ... while such a call runs (_shared_prompt)
+        self._extra_conds = None                         # (conds, weights) of the sample_guided() calls inside `with self.extra_conds(...)`
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -456,6 +478,8 @@ class RQTransformer(Stage2Model):
         ``min_p=`` / ``typical_p=`` (not in the reference; keywords, or ``with self.truncation(min_p=..., typical_p=...)`` around the
         call: see truncation()): min-p and locally typical sampling after top-p."""
         assert self.block_size == partial_sample.shape[1:]
+        if self._extra_conds is not None:
+            raise NotImplementedError('extra_conds() composes guidance: it needs sample_guided() (an unguided call has no pair to fold into)')
         self._cf = None
         (H, W, D) = self.block_size
         if self._schedule:
@@ -637,6 +661,96 @@ class RQTransformer(Stage2Model):
             top_p_list = [min(top_p[i], 1.0) for i in range(D)]
         return top_k_list, top_p_list
 
+    # ------------------------------------------------------------------ composed guidance
+    MAX_EXTRA_CONDS = _native.MAX_EXTRA_CONDS
+
+    @contextlib.contextmanager
+    def extra_conds(self, conds, weights):
+        """Composed guidance (not in the reference): negative prompts and extra conditions for the sample_guided() calls made inside the
+        block.  ``conds``: 1 .. 4 conditionings with the shape and dtype rules of ``cond`` (None = zeros); ``weights``: as many finite
+        floats or (B,) tensors (a weight per image).  With c, u and x_k the raw logits of an image under ``cond``, ``uncond`` and
+        ``conds[k]``, every code is drawn from
+
+            G = u + s (c - u) + sum_k w_k (x_k - u)
+
+        so a negative prompt is an extra condition with w < 0 (``sample_guided(..., negative=n, negative_scale=w)`` is sugar for
+        ``conds=[n], weights=[-w]``) and a second prompt or a style condition one with w > 0.  The loop runs inside the engine over
+        (2 + K) B rows (rqamd_rqt_sample_compose): every block sees exactly the codes that were drawn, and filters, temperature and
+        Philox counters are those of sample_guided().  All weights zero -- or every extra condition equal to ``uncond`` -- draws what
+        the guided call over the same rows draws, bit for bit.  Composes with keep_mask, start_loc, seeds(), per-image parameter
+        tensors, truncation(), schedule() (a guidance schedule applies to s; the weights have no schedule), return_log_probs() (draw
+        under the composed distribution, model / model_uncond raw as without extra conditions), amp and prefix_mode; ``cached=False``
+        is the host loop over the (2 + K) B rows, bit for bit equal to ``cached=True``.  sample(), shared_cond() and ``sampler='torch'``
+        raise NotImplementedError inside the block; a different number of conds and weights, more than 4 of them, a wrong shape or a
+        non-finite weight raise ValueError before anything runs."""
+        conds, weights = list(conds), list(weights)
+        if len(conds) != len(weights):
+            raise ValueError(f'extra_conds: {len(conds)} conds and {len(weights)} weights')
+        if not 1 <= len(conds) <= self.MAX_EXTRA_CONDS:
+            raise ValueError(f'extra_conds: {len(conds)} extra conditions; expected 1 .. {self.MAX_EXTRA_CONDS}')
+        for w in weights:
+            if torch.is_tensor(w):
+                if w.dim() > 1 or w.dtype.is_complex or w.dtype == torch.bool or not bool(torch.isfinite(w.to(torch.float32)).all()):
+                    raise ValueError(f'extra_conds: weight of shape {tuple(w.shape)} / {w.dtype}; expected finite real values, a number or a (B,) tensor')
+            elif not isinstance(w, (int, float)) or isinstance(w, bool) or not math.isfinite(float(w)):
+                raise ValueError(f'extra_conds: weight {w!r}; expected a finite number or a (B,) tensor')
+        saved, self._extra_conds = self._extra_conds, (conds, weights)
+        try:
+            yield self
+        finally:
+            self._extra_conds = saved
+
+    def _compose_args(self, B, device):
+        """self._extra_conds for B images, checked -> None outside extra_conds(), else dict(K=, conds= K (B, block_size_cond) int64 tensors
+        on `device` or None, w= K rows of B floats on the host)"""
+        if self._extra_conds is None:
+            return None
+        conds, weights = self._extra_conds
+        cs, ws = [], []
+        for k, c in enumerate(conds):
+            if c is not None and (not torch.is_tensor(c) or c.shape[0] != B or c.numel() != B * self.block_size_cond):
+                shape = tuple(c.shape) if torch.is_tensor(c) else type(c).__name__
+                raise ValueError(f'extra_conds: conds[{k}] of shape {shape}; expected {(B, self.block_size_cond)} (the shape of cond)')
+            cs.append(self._cond(c, B, device))
+        for k, w in enumerate(weights):
+            if torch.is_tensor(w) and w.dim() == 1:
+                if w.shape[0] != B:
+                    raise ValueError(f'extra_conds: weights[{k}] of shape {tuple(w.shape)}; expected ({B},) (one weight per image)')
+                ws.append([float(v) for v in w.to(torch.float32).tolist()])
+            else:
+                ws.append([float(w)] * B)
+        return dict(K=len(cs), conds=cs, w=ws)
+
+    @staticmethod
+    def _compose_flat(comp):
+        """the arguments of RqtEngine.arm_compose (conds, K * B weights condition-major)"""
+        return comp['conds'], [v for row in comp['w'] for v in row]
+
+    def _compose_rows_cat(self, comp, xs, c, u):
+        """the (2 + K) B rows of the host loops: codes repeated, conditionings cond, uncond, extras (None where every block is zeros)"""
+        B = xs.shape[0]
+        blocks = [c, u] + comp['conds']
+        c2 = None
+        if any(b is not None for b in blocks):
+            zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=xs.device)
+            c2 = torch.cat([zeros if b is None else b for b in blocks])
+        return torch.cat([xs] * len(blocks)), c2
+
+    @staticmethod
+    def _compose_rows(logits, n, comp, scales):
+        """compose_logits over the (2 + K) blocks of n rows of `logits`, with one scale (a float) or one per row (a list): the rows of each
+        distinct scale through the entry point -- elementwise, so row b is what the engine's fold and guided sampler mix for b"""
+        K = comp['K']
+        W = torch.tensor(comp['w'], dtype=torch.float32, device=logits.device)
+        cu, x = logits[:2 * n], logits[2 * n:].reshape(K, n, -1)
+        if not isinstance(scales, (list, tuple)):
+            return _native.compose_logits(cu[:n], cu[n:], x, W, scales)
+        out = torch.empty_like(cu[:n])
+        for s in sorted(set(scales)):
+            idx = torch.tensor([i for i, v in enumerate(scales) if v == s], dtype=torch.long, device=logits.device)
+            out[idx] = _native.compose_logits(cu[:n][idx], cu[n:][idx], x[:, idx], W[:, idx], s)
+        return out
+
     # ------------------------------------------------------------------ per-image sampling parameters
     @contextlib.contextmanager
     def shared_cond(self, n):
@@ -774,12 +888,15 @@ class RQTransformer(Stage2Model):
         xs = partial_sample.to(torch.long).contiguous()
         c = self._cond(cond, B, device)
         u = self._cond(uncond, B, device) if guided else None
+        comp = self._compose_args(B, device) if guided else None
         keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
         if self.sampler == 'torch' or not cached:
             if keep is not None:
                 xs = torch.where(keep, xs, torch.zeros_like(xs))            # (see sample(): the host loops embed every code)
             xs2, c2, scale = xs, c, None
-            if guided:
+            if comp is not None:
+                (xs2, c2), scale = self._compose_rows_cat(comp, xs, c, u), rows['gs']
+            elif guided:
                 xs2, scale = torch.cat([xs, xs]), rows['gs']
                 if c is not None or u is not None:
                     zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
@@ -788,7 +905,8 @@ class RQTransformer(Stage2Model):
             if self.sampler == 'torch':
                 return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, None, None, None, keep, active, scale, rows=dev)
             seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
-            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, None, None, None, seed, offset, keep, active, scale, rows=dev, trunc=trunc)
+            return self._sample_uncached(eng, xs2, c2, cbs, start_loc, None, None, None, seed, offset, keep, active, scale, rows=dev, trunc=trunc,
+                                         comp=comp)
         seed, offset = (0, 0) if rows['seeds'] is not None else self._draw_rng(device, H * W * D)
         keep8, pos_active, start = None, None, start_loc
         if keep is not None:
@@ -800,13 +918,17 @@ class RQTransformer(Stage2Model):
         def run():
             if tr:
                 eng.arm_trunc(*tr)
+            if comp is not None:
+                eng.arm_compose(*self._compose_flat(comp))
             try:
                 return eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None,
                                        rows['seeds'], seed, offset, self.use_graph, **want_logp)
             finally:
                 eng.arm_trunc(None, None)
+                eng.arm_compose()
         return self._with_log_probs(want_logp, self._on_side_stream(device, run))
 
+    @_negative_prompt
     @_truncation_keywords
     @_shared_prompt
     @torch.no_grad()
@@ -823,7 +945,8 @@ class RQTransformer(Stage2Model):
         tensors and ``with self.seeds(...)`` as in sample(); ``guidance_scale`` as a (B,) tensor gives every image its own scale.
         Inside ``with self.return_log_probs():`` the call returns ``(codes, SampleLogProbs(draw, model, model_uncond))``, draw under the
         guided distribution, model / model_uncond under the raw logits of the two twins.  ``min_p`` / ``typical_p`` as in sample(),
-        applied to the guided distribution."""
+        applied to the guided distribution.  ``negative=`` / ``negative_scale=`` (keywords) and ``with self.extra_conds(...)``: negative
+        prompts and extra conditions folded into the guided logits (see extra_conds())."""
         assert self.block_size == partial_sample.shape[1:]
         self._cf = None
         (H, W, D) = self.block_size
@@ -848,6 +971,7 @@ class RQTransformer(Stage2Model):
         cbs = self._checked_codebooks(model_aux)
         xs = partial_sample.to(torch.long).contiguous()
         c, u = self._cond(cond, B, device), self._cond(uncond, B, device)
+        comp = self._compose_args(B, device)
         keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
         if self.sampler == 'torch' or not cached:
             if self.sampler == 'torch' and not cached:
@@ -855,16 +979,19 @@ class RQTransformer(Stage2Model):
             if keep is not None:
                 xs = torch.where(keep, xs, torch.zeros_like(xs))            # (see sample(): the host loops embed every code)
             # the host loops run the engine's unguided entry points over the 2B rows themselves: images under cond, then their twins
+            # (composed guidance: then the K blocks under the extra conditions)
             xs2 = torch.cat([xs, xs])
             c2 = None
-            if c is not None or u is not None:
+            if comp is not None:
+                xs2, c2 = self._compose_rows_cat(comp, xs, c, u)
+            elif c is not None or u is not None:
                 zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
                 c2 = torch.cat([zeros if c is None else c, zeros if u is None else u])
             if self.sampler == 'torch':
                 return self._sample_torch_multinomial(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, keep, active, scale)
             seed, offset = self._draw_rng(device, H * W * D)
             return self._sample_uncached(eng, xs2, c2, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep, active, scale,
-                                         trunc=trunc)
+                                         trunc=trunc, comp=comp)
         seed, offset = self._draw_rng(device, H * W * D)
         keep8, pos_active, start = None, None, start_loc
         if keep is not None:
@@ -876,11 +1003,14 @@ class RQTransformer(Stage2Model):
         def run():
             if tr:
                 eng.arm_trunc(*tr)
+            if comp is not None:
+                eng.arm_compose(*self._compose_flat(comp))
             try:
                 return eng.sample_guided(xs, keep8, pos_active, c, u, cbs, start, temperature, scale, top_k_list, top_p_list, seed, offset,
                                          self.use_graph, **want)
             finally:
                 eng.arm_trunc(None, None)
+                eng.arm_compose()
         return self._with_log_probs(want, self._on_side_stream(device, run))
 
     # ------------------------------------------------------------------ sampling schedules over positions and depths
@@ -1006,12 +1136,13 @@ class RQTransformer(Stage2Model):
         xs = partial_sample.to(torch.long).contiguous()
         c = self._cond(cond, B, device)
         u = self._cond(uncond, B, device) if guided else None
+        comp = self._compose_args(B, device) if guided else None
         keep, active = (None, None) if keep_mask is None else self._keep_flags(keep_mask, xs, start_loc)
         seeded = rows is not None and rows['seeds'] is not None
         seed, offset = (0, 0) if seeded else self._draw_rng(device, H * W * D)
         if not cached:
             return self._sample_uncached_scheduled(eng, xs, c, u, cbs, start_loc, sched, rows, trunc, temperature, top_k_list, top_p_list,
-                                                   guidance_scale if guided else None, seed, offset, keep, active)
+                                                   guidance_scale if guided else None, seed, offset, keep, active, comp=comp)
         nb = B if sched_per_image else 1
         arrays = {name: t.expand(nb, H * W, D).reshape(-1) for name, t in sched.items()}
         tr = self._trunc_engine(trunc)
@@ -1025,6 +1156,8 @@ class RQTransformer(Stage2Model):
             eng.arm_schedule(per_image=sched_per_image, **arrays)
             if tr:
                 eng.arm_trunc(*tr)
+            if comp is not None:
+                eng.arm_compose(*self._compose_flat(comp))
             try:
                 if rows is not None:
                     return eng.sample_rows(xs, keep8, pos_active, c, u, cbs, start, rows['T'], rows['tk'], rows['tp'], rows['gs'] if guided else None,
@@ -1038,10 +1171,11 @@ class RQTransformer(Stage2Model):
             finally:
                 eng.arm_trunc(None, None)            # (a call refused before it reached the library leaves nothing armed)
                 eng.arm_schedule()
+                eng.arm_compose()
         return self._with_log_probs(want, self._on_side_stream(device, run))
 
     def _sample_uncached_scheduled(self, eng, xs, cond, uncond, cbs, start_loc, sched, rows, trunc, temperature, top_k_list, top_p_list,
-                                   guidance_scale, seed, offset, keep, active):
+                                   guidance_scale, seed, offset, keep, active, comp=None):
         """``cached=False`` inside schedule(): _sample_uncached with the values of every step sliced out of the tables the engine fills
         for the cached call -- the schedule where it gives a parameter, else the call's own values, broadcast -- and drawn by
         sample_logits_rows (sample_logits_trunc where a min-p / typical value is on anywhere).  Equal to the cached call bit for bit."""
@@ -1075,7 +1209,9 @@ class RQTransformer(Stage2Model):
         if keep is not None:
             xs = torch.where(keep, xs, torch.zeros_like(xs))                # (see sample(): the host loops embed every code)
         xs2, c2 = xs.clone(), cond
-        if guided:
+        if comp is not None:
+            xs2, c2 = self._compose_rows_cat(comp, xs, cond, uncond)
+        elif guided:
             xs2 = torch.cat([xs, xs])
             if cond is not None or uncond is not None:
                 zeros = torch.zeros((B, self.block_size_cond), dtype=torch.long, device=device)
@@ -1088,7 +1224,9 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(device, lambda: eng.logits(xs2, c2, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
-                if guided:
+                if comp is not None:
+                    logits = self._compose_rows(logits, B, comp, G[:, pos, d].tolist())
+                elif guided:
                     logits = self._guide_rows(logits[:B], logits[B:], G[:, pos, d].tolist())
                 step = dict(seed=seed, offset=offset + pos * D + d)
                 tkd = (T[:, pos, d].contiguous(), K[:, pos, d].contiguous(), P[:, pos, d].contiguous())
@@ -1100,7 +1238,7 @@ class RQTransformer(Stage2Model):
                     idx, _ = _native.sample_logits_rows(logits, *tkd, seeds=seeds_dev, **step)
                 if keep is not None:
                     idx = torch.where(keep[:, h, w, d], xs2[:B, h, w, d], idx)
-                xs2[:, h, w, d] = torch.cat([idx, idx]) if guided else idx
+                xs2[:, h, w, d] = torch.cat([idx] * (xs2.shape[0] // B)) if guided else idx
         return xs2[:B].contiguous() if guided else xs2
 
     def _keep_flags(self, keep_mask, xs, start_loc):
@@ -1136,7 +1274,7 @@ class RQTransformer(Stage2Model):
         return keep, host[:-1].view(H * W, D)
 
     def _sample_uncached(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, seed, offset, keep=None, active=None,
-                         guidance_scale=None, rows=None, trunc=None):
+                         guidance_scale=None, rows=None, trunc=None, comp=None):
         """``cached=False`` (transformers.py:352-356): nothing is carried from one step to the next -- every step recomputes the
         logits of the whole code map from the codes drawn so far (one teacher-forced pass of the engine per step, 256 per
         batch, as slow as the reference's own uncached loop) and samples position (h, w, d) from them with the draw the
@@ -1149,12 +1287,14 @@ class RQTransformer(Stage2Model):
         `keep` has B rows and the first B rows are returned.
         ``rows`` (per-image parameters, _rows_on_device): the draw is sample_logits_rows with the tables of the rows -- and
         guidance_scale a list, one scale per image -- in place of the scalars; with seeds, key seeds[b] and counter pos * D + d.
-        ``trunc`` (_trunc_args): min-p / typical sampling, the draw by sample_logits_trunc with the depth's values (or tables)."""
+        ``trunc`` (_trunc_args): min-p / typical sampling, the draw by sample_logits_trunc with the depth's values (or tables).
+        ``comp`` (_compose_args; with guidance_scale): `xs` / `cond` hold (2 + K) B rows, the K blocks under the extra conditions behind the
+        twins; each step draws from compose_logits of the blocks and writes the code to all of them."""
         from ... import _native
         (H, W, D) = self.block_size
         start = max(int(start_loc[0]) * W + int(start_loc[1]), 0)
         xs = xs.clone()
-        n = xs.shape[0] // 2 if guidance_scale is not None else xs.shape[0]
+        n = xs.shape[0] // (2 + (comp['K'] if comp is not None else 0)) if guidance_scale is not None else xs.shape[0]
         if trunc is not None and rows is not None:
             mp_dev, ty_dev = self._trunc_on_device(trunc, n, D, xs.device)
         for pos in range(start, H * W):
@@ -1165,7 +1305,9 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(xs.device, lambda: eng.logits(xs, cond, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
-                if guidance_scale is not None and rows is not None:
+                if comp is not None:
+                    logits = self._compose_rows(logits, n, comp, guidance_scale)
+                elif guidance_scale is not None and rows is not None:
                     logits = self._guide_rows(logits[:n], logits[n:], guidance_scale)
                 elif guidance_scale is not None:
                     logits = _native.guide_logits(logits[:n].contiguous(), logits[n:].contiguous(), guidance_scale)
@@ -1184,7 +1326,7 @@ class RQTransformer(Stage2Model):
                                                    offset=offset + pos * D + d)
                 if keep is not None:
                     idx = torch.where(keep[:, h, w, d], xs[:n, h, w, d], idx)
-                xs[:, h, w, d] = idx if guidance_scale is None else torch.cat([idx, idx])
+                xs[:, h, w, d] = idx if guidance_scale is None else torch.cat([idx] * (xs.shape[0] // n))
         return xs if guidance_scale is None else xs[:n].contiguous()
 
     def _sample_torch_multinomial(self, eng, xs, cond, cbs, start_loc, temperature, top_k_list, top_p_list, keep=None, active=None,
