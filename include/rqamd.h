@@ -238,7 +238,19 @@ int rqamd_rqt_destroy(rqamd_rqt* h);
  * position counter is set to n0 and the usual loop goes on from there.  For a text-conditioned model the pass replaces the
  * text-only prefill.  Later positions see the same arithmetic through other GEMM tiles: logits differ by rounding, so a draw that was
  * close may come out differently -- filters and Philox counters are the same.  Captured graphs are shared by the two settings; model
- * log-probabilities stay NaN and draw +0.0 at the prefix positions.  Kept runs that are not leading stay stepped. */
+ * log-probabilities stay NaN and draw +0.0 at the prefix positions.  Kept runs that are not leading stay stepped (see below).
+ * "masked.run_prefill" (0 | 1, default 0; additive, ABI v7): how the same entry points bring kept runs that are NOT leading into the
+ * cache.  A position is inactive when no head runs there: it lies before start_h / start_w, or pos_active_host is 0.  0: one body-only
+ * step per inactive position.  1: every maximal run [p0, p1) of inactive positions behind position 0 and behind what "prefix.one_pass"
+ * covered, of two positions at least and with a drawn position after it (p1 < the end of the last active position), goes through the
+ * body stack in ONE pass: R = p1 - p0 tokens per row -- the embeddings of the codes at p0-1 .. p1-2 with their positional entries --
+ * whose keys / values are appended at cache rows block_size_cond - 1 + p0 .. + p1 - 1 behind the rows the earlier positions wrote
+ * (csrc/rqt_attn_extend.hip), rows chunked by "fwd.chunk_rows" in the one-pass forward's workspace; the position counter is set to p1
+ * and the usual loop goes on there.  Guided and composed calls run all their (2 + n_extra) * batch rows through the pass.  Position 0 is
+ * always stepped (its input is the conditioning token), so with "prefix.one_pass" off a leading run is position 0 stepped and positions
+ * 1 .. n0-1 in one pass.  Stepped as before, silently: runs of one position, RQAMD_KV=int8k / int8kv handles, body head sizes other
+ * than 64, shared-prompt calls (rqamd_rqt_sample_shared).  Numerics and graphs as for "prefix.one_pass": same arithmetic through other
+ * GEMM tiles, the same captured graphs in both settings. */
 int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value);
 int rqamd_rqt_set_param(rqamd_rqt* h, const char* name, const float* dev_ptr, const int64_t* shape,
                         int ndim, void* stream);
@@ -458,12 +470,18 @@ int rqamd_rqt_soft_loss(rqamd_rqt* h, const int64_t* codes, const int64_t* cond,
  *                  0 .. n_pos-1 in one pass over the codes of `partial` (see "prefix.one_pass"; the option is not consulted).  Stands
  *                  for step_logits(p, -1), p < n_pos: the next step_logits must be (n_pos, 0) or (n_pos, -1).  n_pos outside
  *                  1 .. H*W-1: RQAMD_ERR_INVALID
+ *   step_run       (additive, ABI v7) stands for step_logits(p, -1), p0 <= p < p1, in one pass over the codes of positions
+ *                  p0-1 .. p1-2 (see "masked.run_prefill"; the option is not consulted; a handle the pass does not serve -- 8-bit
+ *                  cache, body head size other than 64 -- takes the steps themselves).  Valid only when the sequence stands at position
+ *                  p0 with no head step of p0 taken, else RQAMD_ERR_STATE; p0 < 1, p1 <= p0 or p1 > H*W-1: RQAMD_ERR_INVALID.  The
+ *                  next step_logits must be (p1, 0) or (p1, -1)
  *   step_set_code  writes codes[batch] as code (pos, d) of every image
  *   step_end       copies the codes (batch,H,W,D) out (codes_out may be NULL) and ends the sequence.
  * Any other call on the handle ends a sequence in progress. */
 int rqamd_rqt_step_begin(rqamd_rqt* h, const int64_t* partial, const int64_t* cond, int batch,
                          const float* const* codebooks, void* stream);
 int rqamd_rqt_step_prefill(rqamd_rqt* h, int n_pos, void* stream);
+int rqamd_rqt_step_run(rqamd_rqt* h, int p0, int p1, void* stream);
 int rqamd_rqt_step_logits(rqamd_rqt* h, int pos, int d, const float** logits_dev, void* stream);
 int rqamd_rqt_step_set_code(rqamd_rqt* h, int pos, int d, const int64_t* codes, void* stream);
 int rqamd_rqt_step_end(rqamd_rqt* h, int64_t* codes_out, void* stream);
@@ -548,6 +566,13 @@ int rqamd_dbg_rqt_attn_decode(const void* qkv, void* kc, void* vc, float* ksc, f
  * form with another cache pointer; with RQAMD_ERR_UNSUPPORTED: P < 1, P > Tcap, 8-bit caches with P > 255, and the head-size limits above. */
 int rqamd_dbg_rqt_attn_prefill(const void* qkv, void* kc, void* vc, float* ksc, float* vsc, int n_img, int P, int nh, int E, int Tcap,
                                void* y, void* stream);
+/* The causal attention of R new tokens per image behind a cache that already holds rows 0 .. T0-1 (csrc/rqt_attn_extend.hip): qkv
+ * [n_img * R][3E], y [n_img * R][E], caches kc, vc [n_img][nh][Tcap][64] bf16.  Query r attends over cache rows 0 .. T0-1 and over the own
+ * keys 0 .. r of the qkv rows; the k / v of token r are appended at cache row T0 + r.  Rows >= T0 are never read, rows >= T0 + R not
+ * touched.  Output and appended rows are bit for bit those of rqamd_dbg_rqt_attn_prefill over all T0 + R tokens.  Refused before any
+ * launch with RQAMD_ERR_INVALID: a null pointer, n_img, nh, E, R or T0 < 1, T0 + R > Tcap; with RQAMD_ERR_UNSUPPORTED: a head size other
+ * than 64, Tcap > RQAMD_RQT_MAX_CONTEXT.  There are no 8-bit forms. */
+int rqamd_dbg_rqt_attn_extend(const void* qkv, void* kc, void* vc, int n_img, int R, int T0, int nh, int E, int Tcap, void* y, void* stream);
 /* Causal attention inside groups of `group` consecutive rows (the depth axis of the head stack): qkv [rows][3E] -> y [rows][E].
  * Refused with RQAMD_ERR_INVALID: a null qkv or y, E not a multiple of nh, group outside 1 .. 8, rows not a multiple of group. */
 int rqamd_dbg_rqt_attn_packed(const void* qkv, int rows, int group, int nh, int E, void* y, void* stream);

@@ -187,6 +187,10 @@ struct rqamd_rqt {
     // "prefix.one_pass": the given leading positions of a sampling call fill the KV cache in one pass (prefix_prefill) instead of one
     // body-only step each.  Off by default; the captured graphs are the same either way, so the option invalidates nothing
     bool prefix_one_pass = false;
+    // "masked.run_prefill": every kept run of a sampling call that is not leading -- two or more consecutive positions at which no head
+    // runs, behind position 0 and behind whatever "prefix.one_pass" covered, with a drawn position after it -- fills its KV rows in one pass
+    // (run_prefill) instead of one body-only step per position.  Off by default; the position graphs are the same either way
+    bool masked_run_prefill = false;
 };
 
 // -------------------------------------------------------------------------------------------------
@@ -349,6 +353,11 @@ extern "C" int rqamd_rqt_set_option(rqamd_rqt* h, const char* name, int value) {
     if (strcmp(name, "prefix.one_pass") == 0) {  // how the sampling entry points fill the KV cache for the given leading positions (include/rqamd.h)
         if (value != 0 && value != 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: prefix.one_pass = %d (0 or 1)", value);
         h->prefix_one_pass = value == 1;
+        return RQAMD_OK;
+    }
+    if (strcmp(name, "masked.run_prefill") == 0) {  // how the sampling entry points fill the KV cache for kept runs that are not leading (include/rqamd.h)
+        if (value != 0 && value != 1) return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: masked.run_prefill = %d (0 or 1)", value);
+        h->masked_run_prefill = value == 1;
         return RQAMD_OK;
     }
     return rq_fail(RQAMD_ERR_INVALID, "rqt_set_option: unknown option '%s'", name);
@@ -606,7 +615,8 @@ struct Pending { const float* slabs; int n; const float* bias; };   // un-reduce
 
 // one transformer block on `rows` single-token rows; x is the fp32 residual stream (updated lazily:
 // `pend` carries the previous block's fc2 partials + bias into this block's first resid_ln)
-struct PrefillCtx { int img0, n_img, P; bool group = false; };   // non-null: `rows` = n_img * P prefix tokens of images img0.. (multi-token causal attention)
+struct PrefillCtx { int img0, n_img, P; bool group = false; int T0 = 0; };   // non-null: `rows` = n_img * P prefix tokens of images img0.. (multi-token causal attention)
+// T0 > 0 (run_prefill): the P tokens extend caches that hold rows 0 .. T0-1 (rq_launch_attn_extend: head size 64, bf16 / fp16 cache)
 // group (a shared-prompt call): the "images" are groups and their keys / values go to the group caches (L.kcs / L.vcs, capacity P = Tcap)
 // one-pass forward, non-null: `rows` = n_seq sequences of T consecutive rows, causal attention inside each, no KV cache.
 // packed: the head stack's depth groups (T <= 8, a lane per query); else the body stack's (image, token) rows (a lane per query of a
@@ -631,6 +641,12 @@ static int run_block(rqamd_rqt* h, RqtLayer& L, float* x_in, float* x, Pending& 
         AttnPrefillArgs ap{};                      // kc == null: the cache-free form
         ap.qkv = h->qkv; ap.y = h->ya; ap.n_img = op->n_seq; ap.P = op->T; ap.nh = L.nh; ap.E = E; ap.Tcap = op->T;
         RQ_TRY(rq_launch_attn_prefill(ap, st));
+    } else if (pf && pf->T0 > 0) {
+        AttnExtendArgs ae{};
+        const long img_stride = (long)E * Tcap;
+        ae.qkv = h->qkv; ae.y = h->ya; ae.kc = L.kc + pf->img0 * img_stride; ae.vc = L.vc + pf->img0 * img_stride;
+        ae.n_img = pf->n_img; ae.R = pf->P; ae.T0 = pf->T0; ae.nh = L.nh; ae.E = E; ae.Tcap = Tcap;
+        RQ_TRY(rq_launch_attn_extend(ae, st));
     } else if (pf) {
         AttnPrefillArgs ap{};
         const long img_stride = (long)E * Tcap;
@@ -946,6 +962,9 @@ static int begin_batch(rqamd_rqt* h, const StepCtx& c, const int64_t* partial, c
 }
 
 static int prefix_prefill(rqamd_rqt* h, const float* const* codebooks, int B, int n0, hipStream_t st);
+static int run_prefill(rqamd_rqt* h, const float* const* codebooks, int B, int p0, int p1, hipStream_t st);
+// can run_prefill serve this handle?  (rq_launch_attn_extend: head size 64 in the body stack, bf16 / fp16 cache; else the run is stepped)
+static bool run_prefill_ok(const rqamd_rqt* h) { return !h->kv_int8k && !h->body.empty() && h->E == h->body[0].nh * 64; }
 
 // `keep` / `pos_active` (masked sampling): device flags per code, copied into h->keep before anything reads them, and the host's
 // per-position activity (null: every position).  An inactive position has every code given in every row: body stack only, like the
@@ -979,8 +998,22 @@ static int run_all(rqamd_rqt* h, const StepCtx& c_in, const int64_t* partial, co
     }
     const int fam = graph_family(c);
     hipGraphExec_t* gexec = h->gexec[2 * fam + (keep ? 1 : 0)];
+    // "masked.run_prefill": a run [pos, p1) of positions without a head, behind position 0 and behind the prefix, of two positions at least
+    // and with a drawn position after it, goes through the body stack in one pass; the loop goes on at p1.  (A shared-prompt call steps:
+    // its own caches begin behind the group's prefix.)
+    const bool runs = h->masked_run_prefill && !c.fan && run_prefill_ok(h);
+    auto headless = [&](int p) { return !(p >= start_idx && (!pos_active || pos_active[p])); };
     for (int pos = n0; pos < n_pos; ++pos) {
-        const bool do_head = pos >= start_idx && (!pos_active || pos_active[pos]);
+        const bool do_head = !headless(pos);
+        if (runs && !do_head && pos >= 1) {
+            int p1 = pos + 1;
+            while (p1 < n_pos && headless(p1)) ++p1;
+            if (p1 - pos >= 2 && p1 < n_pos) {
+                RQ_TRY(run_prefill(h, c.codebooks, c.B, pos, p1, st));
+                pos = p1 - 1;
+                continue;
+            }
+        }
         const bool graphable = use_graph && c.sample && do_head && pos >= 1 && !h->prof.on;
         if (graphable) {
             if (!h->gvalid) {
@@ -1515,6 +1548,60 @@ static int prefix_prefill(rqamd_rqt* h, const float* const* codebooks, int B, in
     return rq_launch_set_int(h->st, n0, st);
 }
 
+// One-pass fill of a kept run ("masked.run_prefill", rqamd_rqt_step_run): no head runs at spatial positions p0 .. p1-1 (1 <= p0 < p1 < HW)
+// of the B rows in h->xs, so their body tokens need not be stepped.  The R = p1 - p0 tokens of every row -- the inputs of positions
+// p0 .. p1-1, i.e. the embeddings of the codes at p0-1 .. p1-2 with their positional entries; position p0-1 was drawn or kept earlier on
+// the same stream -- run through all body layers at once, and every layer appends K / V at cache rows T0 .. T0+R-1, T0 = cond_len - 1 + p0,
+// behind the rows the earlier positions wrote (rq_launch_attn_extend).  The device position counter is left at p1.
+// Built like prefix_prefill: rows in h->fws (WorkspaceSwap), chunked over images so that n_img * R <= fwd_chunk_rows (one image at
+// least); h->ws / h->kv stay where the captured graphs expect them.  Guided and composed calls pass all their (2 + K) Bs rows: no
+// conditioning token is among a run's inputs, every block's rows attend over the cache rows its own conditioning wrote.
+static int run_prefill(rqamd_rqt* h, const float* const* codebooks, int B, int p0, int p1, hipStream_t st) {
+    const int E = h->E, D = h->D, HW = h->HW, R = p1 - p0, T0 = h->cond_len - 1 + p0;
+    if (p0 < 1 || R < 1 || p1 > HW || B < 1 || B > h->cap) return rq_fail(RQAMD_ERR_INVALID, "rqt run prefill: positions %d .. %d, %d rows (capacity %d)", p0, p1 - 1, B, h->cap);
+    if (!run_prefill_ok(h)) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt run prefill: head size 64 and a bf16 / fp16 cache needed");
+    int n_img = h->fwd_chunk_rows / R;             // images per chunk
+    if (n_img < 1) n_img = 1;
+    if (n_img > B) n_img = B;
+    const size_t rows = (size_t)n_img * R;
+    const size_t total = 2 * al(rows * E * 4) + al((size_t)h->max_slabs * rows * E * 4) + 2 * al(rows * E * 2) + al(rows * 3 * E * 2)
+                         + al(rows * 4 * E * 2) + al(rows * h->Din * 2);
+    RQ_TRY(h->fws.reserve(total));
+    WorkspaceSwap keep(h);
+    char* p = (char*)h->fws.p;
+    auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return (void*)r; };
+    h->x = (float*)take(rows * E * 4); h->xh = (float*)take(rows * E * 4);
+    h->slabs = (float*)take((size_t)h->max_slabs * rows * E * 4);
+    h->y = (bf16_t*)take(rows * E * 2); h->ya = (bf16_t*)take(rows * E * 2);
+    h->qkv = (bf16_t*)take(rows * 3 * E * 2); h->hbuf = (bf16_t*)take(rows * 4 * E * 2);
+    h->ain = (bf16_t*)take(rows * h->Din * 2);
+    for (int b0 = 0; b0 < B; b0 += n_img) {
+        const int n = B - b0 < n_img ? B - b0 : n_img;
+        const int64_t* ccodes = h->xs + (long)b0 * HW * D;
+        BodyInputArgs bi{};
+        bi.bias_tab = h->body_in_bias; bi.pos_tab = h->pos_hw; bi.cond_len = h->cond_len;
+        bi.n_img = n; bi.HW = HW; bi.run_len = R; bi.q0 = p0; bi.D = D; bi.E = E; bi.x = h->x;
+        if (h->in_vq) {
+            GatherCodesArgs g{};
+            g.codes = ccodes; g.head = 0; g.cumsum = 1; g.row0 = 0; g.rows = n * R; g.HW = HW; g.n_pos = R + 1; g.q0 = p0 - 1; g.D = D; g.dim = h->Din; g.out = h->ain;
+            for (int d = 0; d < D; ++d) { g.cb[d] = codebooks[d]; g.K[d] = h->Vd[d]; }
+            RQ_TRY(rq_launch_gather_codes(g, st));
+            RQ_TRY(step_gemm(h, h->ain, h->Din, h->w_in, g.rows, E, h->Din, EPI_F32, nullptr, nullptr, 0, h->xh, E, nullptr, st));
+            bi.emb = h->xh;
+        } else {
+            bi.codes = ccodes; bi.table = h->tok_emb;
+            for (int d = 0; d < D; ++d) { bi.offs[d] = h->tok_offs[d]; bi.V[d] = h->Vd[d]; }
+        }
+        RQ_TRY(rq_launch_body_input(bi, st));
+        Pending pend{nullptr, 0, nullptr};         // (the last layer's fc2 output feeds nothing: no head runs at a position of the run)
+        PrefillCtx pf{b0, n, R};
+        pf.T0 = T0;
+        h->cur_gelu_v2 = h->cfg.gelu_v2 == 1 || h->cfg.gelu_v2 == 3;
+        for (auto& L : h->body) RQ_TRY(run_block(h, L, h->x, h->x, pend, nullptr, n * R, nullptr, 0, 0, h->Tbody, st, &pf));
+    }
+    return rq_launch_set_int(h->st, p1, st);
+}
+
 static int forward_onepass(rqamd_rqt* h, const int64_t* codes, const int64_t* cond, int B, const float* const* codebooks,
                            const OnePassOut& o, hipStream_t st) {
     h->step_on = false;                            // ends a stepping sequence like any other call
@@ -1800,6 +1887,32 @@ extern "C" int rqamd_rqt_step_prefill(rqamd_rqt* h, int n_pos, void* stream) {
     if (h->cap < h->step_B) return rq_fail(RQAMD_ERR_STATE, "rqt_step_prefill: the workspace was re-sized by another call");
     RQ_TRY(prefix_prefill(h, h->step_cb, h->step_B, n_pos, (hipStream_t)stream));
     h->step_pos = n_pos; h->step_d = 0;
+    return RQAMD_OK;
+}
+
+// the body-only steps (p, -1), p0 <= p < p1, of a sequence that stands at position p0 >= 1, in one pass (run_prefill; whatever
+// "masked.run_prefill" says).  A handle run_prefill does not serve (8-bit cache, another head size) takes the steps themselves
+extern "C" int rqamd_rqt_step_run(rqamd_rqt* h, int p0, int p1, void* stream) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_step_run: null handle");
+    if (!h->step_on) return rq_fail(RQAMD_ERR_STATE, "rqt_step_run: no rqamd_rqt_step_begin");
+    if (p0 < 1 || p1 <= p0 || p1 > h->HW - 1)
+        return rq_fail(RQAMD_ERR_INVALID, "rqt_step_run: positions p0 = %d .. p1 = %d outside 1 <= p0 < p1 <= %d", p0, p1, h->HW - 1);
+    if (h->step_pos != p0 || h->step_d != 0)
+        return rq_fail(RQAMD_ERR_STATE, "rqt_step_run: the sequence stands at step (%d, %d), not at position %d with no head step taken", h->step_pos, h->step_d, p0);
+    if (h->cap < h->step_B) return rq_fail(RQAMD_ERR_STATE, "rqt_step_run: the workspace was re-sized by another call");
+    hipStream_t st = (hipStream_t)stream;
+    if (run_prefill_ok(h)) {
+        RQ_TRY(run_prefill(h, h->step_cb, h->step_B, p0, p1, st));
+    } else {
+        StepCtx c{};
+        c.B = h->step_B; c.codebooks = h->step_cb; c.temperature = 1.f; c.sample = false;
+        for (int pos = p0; pos < p1; ++pos) {
+            RQ_TRY(rq_launch_set_int(h->st, pos, st));
+            Pending pend;
+            RQ_TRY(position_body(h, c, false, pos, pend, st));
+        }
+    }
+    h->step_pos = p1; h->step_d = 0;
     return RQAMD_OK;
 }
 

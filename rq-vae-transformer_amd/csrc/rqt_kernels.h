@@ -76,6 +76,19 @@ struct AttnPrefillArgs {
     int n_img, P, nh, E, Tcap;
 };
 
+// Multi-token causal attention that extends a cache which already holds rows 0 .. T0-1 (rqt_attn_extend.hip; the one-pass fill of an
+// interior kept run, engine_rqt.hip: run_prefill): query r of the R new tokens attends over the cached rows and the run's own keys
+// 0 .. r, token r is appended at cache row T0 + r.  Head size 64, bf16 / fp16, T0 + R <= Tcap <= RQAMD_RQT_MAX_CONTEXT.  Bit for bit the
+// rows R of the prefill kernels over T0 + R tokens.
+struct AttnExtendArgs {
+    const bf16_t* qkv;      // [n_img * R][3E], row = img * R + r
+    bf16_t* kc;             // K cache of the FIRST image of this chunk: [n_img][nh][Tcap][64]; rows < T0 are read, rows T0 .. T0+R-1 written
+    bf16_t* vc;
+    bf16_t* y;              // [n_img * R][E]
+    int n_img, R, T0, nh, E, Tcap;
+};
+int rq_launch_attn_extend(const AttnExtendArgs& a, hipStream_t s);
+
 struct EmbedTokArgs {
     const int64_t* xs;      // [rows][HW][D] codes
     const float* cb[8];     // per-depth codebooks (K, dim), padding row excluded
@@ -238,6 +251,8 @@ struct GatherCodesArgs {
     long row0;              // first row of this launch (rows are counted from the start of the chunk)
     int rows, HW, D, dim;
     int n_pos;              // body form: positions per image, n_pos - 1 rows each (2 .. HW); the head form ignores it
+    int q0;                 // body form: the first code position of every image, rows q = q0 .. q0 + n_pos - 2 (0 everywhere but in the run form
+                            // of engine_rqt.hip: run_prefill; q0 + n_pos <= HW)
     bf16_t* out;            // [rows][dim]
 };
 int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s);
@@ -256,6 +271,8 @@ struct BodyInputArgs {
     const float* pos_tab;   // [HW][E] (pos_emb_hw)
     int n_img, HW, D, E;
     int n_pos;              // positions per image, 1 .. HW (HW is the stride of `codes` and the height of the tables)
+    int run_len, q0;        // run form (run_len > 0; engine_rqt.hip: run_prefill): rows (image, r), r = 0 .. run_len-1, are the inputs of positions
+                            // q0 + r (q0 >= 1): the embedding of the codes at q0 - 1 + r, emb [n_img * run_len][E]; cond and n_pos are unused.  0: the forms above
     float* x;               // [n_img * Tb][E]
 };
 int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s);

@@ -2585,7 +2585,7 @@ __global__ void gather_codes_kernel(GatherCodesArgs p) {
         lo = p.cumsum ? 0 : (hi > 0 ? hi - 1 : 0);
     } else {
         const long img = R / (p.n_pos - 1);
-        cpos = img * p.HW + (R - img * (p.n_pos - 1));
+        cpos = img * p.HW + p.q0 + (R - img * (p.n_pos - 1));
         lo = 0; hi = p.D;
     }
     const int64_t* codes = p.codes + cpos * p.D;
@@ -2608,14 +2608,17 @@ __global__ void gather_codes_kernel(GatherCodesArgs p) {
 int rq_launch_gather_codes(const GatherCodesArgs& a, hipStream_t s) {
     if (a.dim % 8 != 0) return rq_fail(RQAMD_ERR_UNSUPPORTED, "embed: dim %d %% 8 != 0", a.dim);
     if (a.rows < 1) return RQAMD_OK;
-    if (!a.head && (a.n_pos < 2 || a.n_pos > a.HW)) return rq_fail(RQAMD_ERR_INVALID, "gather_codes: %d positions per image (2 .. %d)", a.n_pos, a.HW);
+    if (!a.head && (a.n_pos < 2 || a.q0 < 0 || a.n_pos > a.HW - a.q0))
+        return rq_fail(RQAMD_ERR_INVALID, "gather_codes: %d positions per image from position %d (2 .. %d)", a.n_pos, a.q0, a.HW);
     const long n = (long)a.rows * (a.dim / 8);
     RQ_LAUNCH(gather_codes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return rq_check_launch("gather_codes_kernel");
 }
 
 __global__ void body_input_kernel(BodyInputArgs p) {
-    const int per_row = p.E / 4, Tb = p.cond_len - 1 + p.n_pos;
+    // run form (run_len > 0): no conditioning tokens -- row (image, r) is the input of spatial position q0 + r, i.e. the embedding of the
+    // codes at q = q0 - 1 + r, and emb holds run_len rows per image
+    const int per_row = p.E / 4, Tb = p.run_len > 0 ? p.run_len : p.cond_len - 1 + p.n_pos;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)p.n_img * Tb * per_row) return;
     const long row = gid / per_row;
@@ -2623,7 +2626,20 @@ __global__ void body_input_kernel(BodyInputArgs p) {
     const long img = row / Tb;
     const int t = (int)(row - img * Tb);
     f32x4 v;
-    if (t < p.cond_len) {
+    if (p.run_len > 0) {
+        const int q = p.q0 - 1 + t;
+        if (p.table) {
+            const int64_t* codes = p.codes + (img * p.HW + q) * p.D;
+            v = *(const f32x4*)(p.pos_tab + (long)q * p.E + c);
+            for (int d = 0; d < p.D; ++d) {
+                const long code = codes[d];
+                if (code < 0 || code >= p.V[d]) rq_trap();          // index error in the reference (nn.Embedding)
+                v = v + *(const f32x4*)(p.table + ((long)p.offs[d] + code) * p.E + c);
+            }
+        } else {
+            v = *(const f32x4*)(p.emb + row * p.E + c) + *(const f32x4*)(p.bias_tab + (long)q * p.E + c);
+        }
+    } else if (t < p.cond_len) {
         long cc = p.cond ? p.cond[img * p.cond_stride + t] : 0;
         if (cc < 0) cc = 0;
         if (cc >= p.vocab_cond) cc = p.vocab_cond - 1;
@@ -2645,8 +2661,10 @@ __global__ void body_input_kernel(BodyInputArgs p) {
     *(f32x4*)(p.x + row * p.E + c) = v;
 }
 int rq_launch_body_input(const BodyInputArgs& a, hipStream_t s) {
-    if (a.n_pos < 1 || a.n_pos > a.HW) return rq_fail(RQAMD_ERR_INVALID, "body_input: %d positions per image (1 .. %d)", a.n_pos, a.HW);
-    const long n = (long)a.n_img * (a.cond_len - 1 + a.n_pos) * (a.E / 4);
+    if (a.run_len > 0) {
+        if (a.q0 < 1 || a.run_len > a.HW - a.q0) return rq_fail(RQAMD_ERR_INVALID, "body_input: a run of %d positions from position %d (map of %d)", a.run_len, a.q0, a.HW);
+    } else if (a.n_pos < 1 || a.n_pos > a.HW) return rq_fail(RQAMD_ERR_INVALID, "body_input: %d positions per image (1 .. %d)", a.n_pos, a.HW);
+    const long n = (long)a.n_img * (a.run_len > 0 ? a.run_len : a.cond_len - 1 + a.n_pos) * (a.E / 4);
     RQ_LAUNCH(body_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     return rq_check_launch("body_input_kernel");
 }

@@ -113,6 +113,7 @@ _SIGS = {
                                       C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_begin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_prefill': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'rqamd_rqt_step_run': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'rqamd_rqt_step_logits': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     'rqamd_rqt_step_set_code': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_rqt_step_end': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -138,6 +139,8 @@ _SIGS = {
                                             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_dbg_rqt_attn_prefill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p]),
+    'rqamd_dbg_rqt_attn_extend': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p]),
     'rqamd_dbg_rqt_attn_packed': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_dbg_rqt_attn_shared': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -146,7 +149,8 @@ EXPORTS = tuple(_SIGS)
 
 
 EXPORTS_F16 = tuple(n for n in _SIGS if n.startswith('rqamd_rqt_') or n.startswith('rqamd_vae_')) + ('rqamd_abi_version', 'rqamd_last_error', 'rqamd_dbg_set_row_scale',
-                                                                                                           'rqamd_dbg_rqt_attn_decode', 'rqamd_dbg_rqt_attn_shared')
+                                                                                                           'rqamd_dbg_rqt_attn_decode', 'rqamd_dbg_rqt_attn_shared',
+                                                                                                           'rqamd_dbg_rqt_attn_prefill', 'rqamd_dbg_rqt_attn_extend')
 
 
 def _bind(path, names=None):
@@ -682,13 +686,26 @@ def dbg_rqt_attn_shared(qkv, kcs, vcs, kc, vc, y, fan, nh, t, t_max=-1, step=Non
     return y
 
 
-def dbg_rqt_attn_prefill(qkv, y, n_img, P, nh, Tcap, kc=None, vc=None, ksc=None, vsc=None):
+def dbg_rqt_attn_prefill(qkv, y, n_img, P, nh, Tcap, kc=None, vc=None, ksc=None, vsc=None, half=False):
     """diagnostics: the causal prefix attention alone (rqamd_dbg_rqt_attn_prefill).  qkv (n_img * P, 3E) bf16, y (n_img * P, E) bf16,
-    caches as dbg_rqt_attn_decode with rows = n_img, or none at all (the cache-free form)."""
+    caches as dbg_rqt_attn_decode with rows = n_img, or none at all (the cache-free form).  half: the fp16 build, as there."""
+    L, dt = (lib16(), torch.float16) if half else (lib(), torch.bfloat16)
     with on_device_of(qkv):
-        check(lib().rqamd_dbg_rqt_attn_prefill(ptr(qkv, torch.bfloat16), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
-                                               int(n_img), int(P), int(nh), qkv.shape[-1] // 3, int(Tcap), ptr(y, torch.bfloat16),
-                                               stream_of(qkv)))
+        check(L.rqamd_dbg_rqt_attn_prefill(ptr(qkv, dt), ptr(kc), ptr(vc), ptr(ksc, torch.float32), ptr(vsc, torch.float32),
+                                           int(n_img), int(P), int(nh), qkv.shape[-1] // 3, int(Tcap), ptr(y, dt),
+                                           stream_of(qkv)), L)
+    return y
+
+
+def dbg_rqt_attn_extend(qkv, kc, vc, y, n_img, R, T0, nh, Tcap, half=False):
+    """diagnostics: the cache-extending causal attention alone (rqamd_dbg_rqt_attn_extend, csrc/rqt_attn_extend.hip).  qkv (n_img * R, 3E)
+    and y (n_img * R, E) bf16, caches (n_img, nh, Tcap, 64) bf16 holding rows 0 .. T0-1 -- or, half, torch.float16 through the fp16 build.
+    Query r attends over cache rows < T0 and own keys 0 .. r; token r is appended at cache row T0 + r."""
+    L, dt = (lib16(), torch.float16) if half else (lib(), torch.bfloat16)
+    dev_t = qkv if qkv is not None else y
+    with on_device_of(dev_t):
+        check(L.rqamd_dbg_rqt_attn_extend(ptr(qkv, dt), ptr(kc, dt), ptr(vc, dt), int(n_img), int(R), int(T0), int(nh),
+                                          (qkv.shape[-1] // 3) if qkv is not None else y.shape[-1], int(Tcap), ptr(y, dt), stream_of(dev_t)), L)
     return y
 
 
@@ -1213,6 +1230,19 @@ class RqtEngine(_Engine):
         with on_device_of(dev):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0)
             check(self._L.rqamd_rqt_step_prefill(self._h, int(n_pos), st), self._L)
+
+    def step_run(self, p0, p1):
+        """at position p0 >= 1 with no head step of p0 taken: the KV cache of positions p0 .. p1-1 from the codes in one pass
+        (rqamd_rqt_step_run) -- stands for step_logits(p, -1), p0 <= p < p1; the next step is (p1, 0)"""
+        step = getattr(self, '_step', None)
+        dev = step[1] if step else self.device
+        with on_device_of(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0)
+            check(self._L.rqamd_rqt_step_run(self._h, int(p0), int(p1), st), self._L)
+
+    def attn_extend(self, qkv, kc, vc, y, n_img, R, T0, nh, Tcap):
+        """the cache-extending attention alone in this engine's build (bf16, or fp16 behind half=True): dbg_rqt_attn_extend"""
+        return dbg_rqt_attn_extend(qkv, kc, vc, y, n_img, R, T0, nh, Tcap, half=self.half)
 
     def step_logits(self, pos, d):
         """logits (B, V) fp32 of step (pos, d) -- a view of the engine's workspace, valid until the next engine call; d < 0:

@@ -183,6 +183,12 @@ class RQTransformer(Stage2Model):
         # GEMM tiles: the codes drawn after the prefix differ from the stepped mode's wherever a draw was close; filters and Philox
         # counters are the same.  sample(cached=False) has no cache and is untouched.
         self.prefix_mode = os.environ.get('RQAMD_PREFIX', 'stepped')
+        # how the same calls bring kept runs that are NOT leading (keep_mask: the left columns of every row, the rows between two drawn
+        # bands, the rim of a hole -- positions whose codes are kept in every image) into the cache: 'stepped' (default): one body-only
+        # step per position; 'one_pass' (or RQAMD_KEPT_RUNS=one_pass): every such run of two positions or more through the body stack
+        # at once (engine option "masked.run_prefill" / rqamd_rqt_step_run).  Independent of prefix_mode; numerics as there.  8-bit
+        # caches (RQAMD_KV), body head sizes other than 64 and shared_cond() calls stay stepped.
+        self.kept_run_mode = os.environ.get('RQAMD_KEPT_RUNS', 'stepped')
         self._return_log_probs = False                   # inside `with self.return_log_probs()`: sample() also returns SampleLogProbs
         self._image_seeds = None                         # per-image Philox seeds of the sample() calls inside `with self.seeds(...)`
         self._truncation = (None, None)                  # (min_p, typical_p) of the sample() calls inside `with self.truncation(...)`
@@ -243,16 +249,24 @@ class RQTransformer(Stage2Model):
             raise ValueError(f"prefix_mode = {self.prefix_mode!r} ('stepped' or 'one_pass')")
         return self.prefix_mode == 'one_pass'
 
+    def _kept_runs_one_pass(self):
+        if self.kept_run_mode not in ('stepped', 'one_pass'):
+            raise ValueError(f"kept_run_mode = {self.kept_run_mode!r} ('stepped' or 'one_pass')")
+        return self.kept_run_mode == 'one_pass'
+
     def _sampling_eng(self, amp=False):
-        """_eng(amp) with the engine's "prefix.one_pass" option following self.prefix_mode (touched only when it has to change: a
-        handle of a model that never leaves the default never sees the option), and -- inside shared_cond(n) only -- armed for a
+        """_eng(amp) with the engine's "prefix.one_pass" / "masked.run_prefill" options following self.prefix_mode / self.kept_run_mode
+        (touched only when they have to change: a handle of a model that never leaves the default never sees the options), and -- inside shared_cond(n) only -- armed for a
         shared-prompt call (the call consumes the arming, and _shared_prompt disarms whatever a refused call left: outside the context
         the engine is not touched)"""
-        want = self._prefix_one_pass()
+        want, want_runs = self._prefix_one_pass(), self._kept_runs_one_pass()
         eng = self._eng(amp)
         if getattr(eng, '_prefix_one_pass', False) != want:
             eng.set_option('prefix.one_pass', int(want))
             eng._prefix_one_pass = want
+        if getattr(eng, '_kept_runs_one_pass', False) != want_runs:
+            eng.set_option('masked.run_prefill', int(want_runs))
+            eng._kept_runs_one_pass = want_runs
         if self._shared_live:
             eng.arm_shared(self._shared_live)           # the next sampling call of the engine is a shared-prompt call
         return eng
