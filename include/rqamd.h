@@ -332,6 +332,48 @@ int rqamd_rqt_sample_compose(rqamd_rqt* h, int n_extra, const int64_t* const* ex
  * host-driven loops over (2 + n_extra) * batch rows and for tests; the engine folds into its own scratch and never calls it. */
 int rqamd_compose_logits(const float* cond_logits, const float* uncond_logits, const float* extra_logits, int n_extra,
                          const float* extra_weight, int rows, int vocab, float scale, float* out, void* stream);
+/* Anchored sampling: draw codes near an encoded image inside the engine (not in the reference); additive, ABI v7.  Arms the NEXT
+ * rqamd_rqt_sample, _masked, _guided or _rows call on the handle; that call consumes the arming whether it succeeds or fails.
+ * z = NULL disarms.  z: DEVICE, (batch, H, W, dim) fp32, the output of RQVAE.encode in code shape, copied into the handle by the armed
+ * call.  codebooks / code_norms: D DEVICE pointers each (the two pointer arrays are copied when the call arms), every codebook exactly
+ * `vocab_size` codes of width dim and 16-byte aligned like z, the norms from rqamd_rq_code_norms.  weight: HOST array of H * W * D values >= 0 (per_image = 0: one
+ * table for all images) or batch * H * W * D values (per_image = 1, image-major, depth last), read and checked by the armed call.
+ * At every head step the logits of image b get the quantiser's soft-code term of the residual the image has at that depth given the
+ * codes drawn (or kept) so far:
+ *     x'[v] = x[v] - w(b, p, d) * dist(r_d(b, p), codebook_d[v]),    r_0 = z[b, p, :],   r_{d+1} = r_d - codebook_d[code(b, p, d)]
+ * dist the expanded-form squared distance in fp32 (the values of rqamd_rq_distances over the same rows, bit for bit), the residual
+ * subtracted one depth after the other in fp32 as rqamd_rq_quantize does.  w = 0 is the prior, w -> inf the codes of rqamd_rq_quantize, and
+ * in between the distribution is p_model * softmax(-dist / temp) with w = 1 / temp: get_soft_codes as a likelihood.  In fp32,
+ *     x' = (x == -inf || w == 0 || dist is not finite) ? x : fmaf(-w, dist, x)
+ * -- LogitMask columns stay -inf; w == 0 leaves the logit bit for bit (-0.0 included), so an all-zero table draws what the unarmed call
+ * draws; a distance that is NaN or infinite (a non-finite z row; never with finite z) leaves the logit alone, so that image degrades to
+ * unanchored.  Guided calls: both twins of a pair get the same term before guide(), so the guided mix is shifted by -w * dist up to
+ * rounding.  Three launches per head step (csrc/rqt_anchor.hip: residual, the quantiser's distance kernel, fold) into memory of the
+ * handle; the sampler kernels, filters, temperature and Philox counters are those of the unarmed call.  It composes with keep (the
+ * residual follows the given code), start_h / start_w, "prefix.one_pass" and "masked.run_prefill" (no head step, no anchor), per-image
+ * parameters and seeds, rqamd_rqt_sample_logp (draw: under the anchored distribution after all stages; model / model_uncond: the raw
+ * logits, as without an anchor), _trunc and _schedule.
+ * Anchored calls replay graph sets of their own, keyed on the codebook and norms pointers and dim next to the fields of the family the
+ * call would otherwise belong to; z and the weights live in memory of the handle and are in no key: alternating anchored and plain
+ * calls recaptures nothing, a new z or new weights recapture nothing.
+ * Refused before anything is enqueued, RQAMD_ERR_INVALID: a weight that is negative or not finite, null weights, a null codebook or
+ * norms pointer; RQAMD_ERR_UNSUPPORTED: dim other than 64 / 128 / 192 / 256, depths with different vocabularies (vocab_sizes[d] <
+ * vocab_size), an arming together with rqamd_rqt_sample_shared or rqamd_rqt_sample_compose. */
+int rqamd_rqt_sample_anchor(rqamd_rqt* h, const float* z, const float* const* codebooks, const float* const* code_norms, int dim,
+                            const float* weight, int per_image);
+/* The three stages of ONE anchored step over given rows, through the kernels and the device function of rqamd_rqt_sample_anchor: for
+ * host-driven loops and for tests.  logits, out (rows, vocab) fp32; logits_u / out_u the unconditional twins, both or neither; z_rows
+ * (rows, dim) fp32 and 16-byte aligned; codes (rows, d) int64, the codes of depths 0 .. d-1 (NULL with d = 0; a code outside
+ * 0 .. vocab-1 traps); codebooks / code_norms: d + 1 DEVICE pointers each, `vocab` codes of width dim (64 / 128 / 192 / 256), the
+ * codebooks 16-byte aligned (RQAMD_ERR_INVALID otherwise, as for z_rows and resid_out); weight:
+ * DEVICE, rows values (not checked).  resid_out (rows, dim) and dist_out (rows, vocab), each or NULL: the residual and the distances of
+ * the step.  workspace: 16-byte aligned DEVICE memory, 256-byte rounded rows * 512 bytes, plus rows * dim * 4 (256-byte rounded) without
+ * resid_out, plus rows * vocab * 4 without dist_out.  All contiguous device memory; 16-byte accesses in the fold when vocab % 4 == 0
+ * and the bases are aligned. */
+int rqamd_anchor_logits(const float* logits, const float* logits_u, const float* z_rows, const int64_t* codes,
+                        const float* const* codebooks, const float* const* code_norms, int d, int dim, int vocab, const float* weight,
+                        int rows, float* out, float* out_u, float* resid_out, float* dist_out, void* workspace, int64_t workspace_bytes,
+                        void* stream);
 /* Sampling parameters per image (not in the reference); additive, ABI v7.  One entry point for plain, masked and guided sampling:
  * keep NULL: unmasked (pos_active_host is ignored), else as in rqamd_rqt_sample_masked; uncond NULL and guidance_scale NULL: unguided,
  * else as in rqamd_rqt_sample_guided (uncond NULL = zeros; uncond without guidance_scale is RQAMD_ERR_INVALID).

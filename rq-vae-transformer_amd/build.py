@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'librqamd.so')
-SOURCES = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_attn_shared.hip', 'rqt_attn_extend.hip', 'rqt_compose.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip',
+SOURCES = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_attn_shared.hip', 'rqt_attn_extend.hip', 'rqt_compose.hip', 'rqt_anchor.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip',
            'engine_vae.hip']
 # sources that #include another .hip (the sampler section of rqt_kernels.hip, instantiated once more): rebuilt when that file changes
 INCLUDES = {'rqt_sample_guided.hip': ['rqt_kernels.hip'], 'rqt_sample_rows.hip': ['rqt_kernels.hip'], 'rqt_sample_logp.hip': ['rqt_kernels.hip'],
@@ -20,7 +20,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 # opt-in RQAMD_VAE=fp16 RQ-VAE engine runs on.  Same C ABI (the rqamd_rqt_* / rqamd_vae_* entry points, rqamd_abi_version,
 # rqamd_last_error); the quantiser (fp32 arithmetic, the same code in both) is in it for rqamd_rqt_soft_loss, which forms soft targets from features.
 OUT_F16 = os.path.join(HERE, 'librqamd_f16.so')
-SOURCES_F16 = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_attn_shared.hip', 'rqt_attn_extend.hip', 'rqt_compose.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip', 'engine_vae.hip']
+SOURCES_F16 = ['api.hip', 'gemm.hip', 'quantize.hip', 'rqt_kernels.hip', 'rqt_attn_shared.hip', 'rqt_attn_extend.hip', 'rqt_compose.hip', 'rqt_anchor.hip', 'rqt_sample_guided.hip', 'rqt_sample_rows.hip', 'rqt_sample_logp.hip', 'rqt_sample_trunc.hip', 'rqt_sample_sched.hip', 'engine_rqt.hip', 'vae_kernels.hip', 'conv_halo.hip', 'engine_vae.hip']
 
 
 def _newer(a, b):

@@ -20,6 +20,7 @@
 // (rqamd_rqt_logits / rqamd_rqt_forward: B rows per launch, the kernels sampling uses) and ONE pass over all positions
 // (forward_onepass below: rqamd_rqt_forward_onepass / rqamd_rqt_log_probs, no KV cache, a workspace of its own).
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "gemm.h"
@@ -129,6 +130,19 @@ struct rqamd_rqt {
     float *cmp_logits = nullptr, *cmp_w = nullptr;
     size_t cmp_rows = 0;            // images the two hold
     std::vector<float> cmp_host;    // host staging of the weight table, like row_host
+    // anchored sampling (rqamd_rqt_sample_anchor): the arming -- z and the codebooks / norms (device pointers, the two pointer ARRAYS copied
+    // when the call arms) and the HOST weights (HW * D, per_image: batch * HW * D, read by the next sampling call) -- and what the three
+    // launches per head step of such a call use (rqt_anchor.hip), one block of memory of the handle's own, allocated by the first
+    // anchored call outside any capture and kept: the logits scratch (rows * V floats, rows = the images, twice that for guided calls),
+    // the distances (images * V), the residual (images * dim), the partial minima of the distance kernel (images * 64 * 8 bytes), the copy
+    // of z (images * HW * dim) and the weight table (images * HW * D; a shared table is repeated for every image, so the captured fold
+    // launches hold one row stride).  It grows with the batch or the width of z, which drops the anchored graphs that hold its addresses
+    struct AnchorArm { const float* z; const float* cb[8]; const float* cn[8]; int dim; const float* weight; int per_image; int bad; } aarm = {};
+    DevBuf anc_buf;
+    float *anc_logits = nullptr, *anc_dist = nullptr, *anc_resid = nullptr, *anc_pv = nullptr, *anc_z = nullptr, *anc_w = nullptr;
+    int* anc_pi = nullptr;
+    size_t anc_imgs = 0, anc_lrows = 0, anc_dim = 0;      // images, logits rows and width of z the block holds
+    std::vector<float> anc_host;    // host staging of the weight table, like row_host
     int max_slabs = 8;
     int cur_gelu_v2 = 0;   // GELU form of the stack being run (cfg.gelu_v2: 0 both erf, 1 both sigmoid, 2 body erf / head sigmoid, 3 body sigmoid / head erf)
     bool kv_int8k = false;   // RQAMD_KV=int8k / int8kv when the handle was created: body-stack keys cached as 64 bytes + one fp32 scale (rqt_kernels.hip)
@@ -163,9 +177,16 @@ struct rqamd_rqt {
     // once more, keys NFAM .. 2 * NFAM - 1 and sets 2 * NFAM .. 4 * NFAM - 1 (graph_family); the group size is part of their key.
     // Composed calls (rqamd_rqt_sample_compose: (2 + K) B rows, a fold launch per head step, the sampler reads the scratch) are every family
     // a third time, keys 2 * NFAM .. 3 * NFAM - 1 and sets 4 * NFAM .. 6 * NFAM - 1; K is part of their key next to the rows, no weight is.
-    hipGraphExec_t gexec[6 * NFAM][NGRAPH] = {};
-    struct Key { int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; int fan; int n_extra; } gkey[3 * NFAM];
-    bool gkey_set[3 * NFAM] = {}, gstale[3 * NFAM] = {};
+    // Anchored calls (rqamd_rqt_sample_anchor: three more launches per head step, the sampler reads the scratch) are every family a fourth
+    // time, keys 3 * NFAM .. 4 * NFAM - 1 and sets 6 * NFAM .. 8 * NFAM - 1.  Next to the fields of the family the call would otherwise
+    // belong to, their key holds the codebook and norms pointers of the arming and the width of z (kernel arguments of the captured
+    // launches, as `cb` is); z and the weights live in memory of the handle and are in no key.
+    hipGraphExec_t gexec[8 * NFAM][NGRAPH] = {};
+    struct Key {
+        int B; float T; float gs; int guided; int tk[8]; float tp[8]; const float* cb[8]; void* stream; float mp[8]; float typ[8]; int fan; int n_extra;
+        const float* acb[8]; const float* acn[8]; long adim;
+    } gkey[4 * NFAM];
+    bool gkey_set[4 * NFAM] = {}, gstale[4 * NFAM] = {};
     bool gvalid = false;
     int64_t n_capture = 0;     // position graphs captured over the life of the handle (rqamd_rqt_graph_captures)
 
@@ -715,6 +736,11 @@ struct StepCtx {
     bool sched_per_image;  //   h->sch_image (a schedule per image) or h->sch_shared (one for all rows); trunc: the min-p / typical tables are read too
     int n_extra;           // composed call (rqamd_rqt_sample_compose): K extra row blocks behind the twins, B = (2 + K) * Bs rows; 0: none
     const int64_t* const* extra_cond;   //   their conditionings (Bs rows each, null entries: zeros)
+    bool anchor;           // anchored call (rqamd_rqt_sample_anchor): residual, distance and fold launches per head step (rqt_anchor.hip), the sampler
+                           //   reads the scratch; h->anc_w holds a weight per (image, position, depth) whatever the arming gave
+    const float* const* acb;   // its codebooks and norms (D device pointers each) and the width of z
+    const float* const* acn;
+    int adim;
     int fan;               // shared-prompt call (rqamd_rqt_sample_shared): rows per group, `cond` / `uncond` hold B / fan (guided: Bs / fan) rows; 0: a plain call
     float* logits_out;     // teacher-forced: (B,HW,D,V)
     float* cond_logits_out; // teacher-forced, text-conditioned: (B, cond_len-1, vocab_size_cond) or null
@@ -817,6 +843,21 @@ static int position_depth(rqamd_rqt* h, const StepCtx& c, int d, const Pending& 
             RQ_TRY(rq_launch_compose(f, st));
             s.logits = f.out_c; s.logits_u = f.out_u; s.out_mirror_n = c.n_extra;
         }
+        if (c.anchor) {
+            // anchored sampling: the residual of every image at this depth from z and the codes of the position so far, its distances to
+            // the codebook of the depth, and the fold of both twins into the scratch (h->logits stays raw for the step's log_prob launch)
+            const int n = c.guided ? c.Bs : B;
+            AnchorResidArgs r{};
+            r.z = h->anc_z; r.z_stride = (long)h->HW * c.adim; r.codes = h->xs; r.code_stride = (long)h->HW * h->D; r.code_D = h->D; r.pos = h->st;
+            r.K = h->V; r.d = d; r.dim = c.adim; r.rows = n; r.out = h->anc_resid;
+            for (int j = 0; j < d; ++j) r.cb[j] = c.acb[j];
+            AnchorFoldArgs f{};
+            f.c = s.logits; f.u = c.guided ? s.logits_u : nullptr; f.dist = h->anc_dist; f.w = h->anc_w;
+            f.w_row_stride = (long)h->HW * h->D; f.pos = h->st; f.D = h->D; f.d = d; f.rows = n; f.V = h->V;
+            f.out_c = h->anc_logits; f.out_u = c.guided ? h->anc_logits + (long)n * h->V : nullptr;
+            RQ_TRY(rq_launch_anchor_step(r, c.acb[d], c.acn[d], h->anc_dist, h->anc_pv, h->anc_pi, f, st));
+            s.logits = f.out_c; s.logits_u = f.out_u;
+        }
         if (c.sched) {         // every value from the tables of the schedule, at (row, *st, d); the scalars are unused
             const rqamd_rqt::SchedTables& t = c.sched_per_image ? h->sch_image : h->sch_shared;
             s.temperature = 1.f; s.top_k = 0; s.top_p = -1.f;
@@ -861,8 +902,10 @@ static int step_family(const StepCtx& c) {
 }
 
 // the key / graph-set family of a call: shared-prompt calls have every family of step_family once more
-// (and composed calls a third time; a call is never both)
-static int graph_family(const StepCtx& c) { return step_family(c) + (c.fan ? rqamd_rqt::NFAM : c.n_extra ? 2 * rqamd_rqt::NFAM : 0); }
+// (composed calls a third time and anchored calls a fourth; a call is only ever one of the three)
+static int graph_family(const StepCtx& c) {
+    return step_family(c) + (c.fan ? rqamd_rqt::NFAM : c.n_extra ? 2 * rqamd_rqt::NFAM : c.anchor ? 3 * rqamd_rqt::NFAM : 0);
+}
 
 // everything that happens at one spatial position (position read from h->st[0] on the device)
 static int position_sequence(rqamd_rqt* h, const StepCtx& c, bool first_pos, bool do_head, int host_pos, hipStream_t st) {
@@ -1078,7 +1121,7 @@ static rqamd_rqt::LogpArm take_arm(rqamd_rqt* h) {
 }
 struct ArmGuard {          // an entry point that returns before sample_impl still consumes the armings
     rqamd_rqt* h;
-    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; h->shared_fan = 0; h->carm = {}; } }
+    ~ArmGuard() { if (h) { h->arm = {}; h->tarm = {}; h->sarm = {}; h->shared_fan = 0; h->carm = {}; h->aarm = {}; } }
 };
 
 // rqamd_rqt_sample / rqamd_rqt_sample_masked / rqamd_rqt_sample_guided / rqamd_rqt_sample_rows behind their argument checks.  `guided`: `batch` images run as
@@ -1098,7 +1141,24 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     h->shared_fan = 0;
     const rqamd_rqt::ComposeArm carm = h->carm;
     h->carm = {};
+    const rqamd_rqt::AnchorArm aarm = h->aarm;
+    h->aarm = {};
     const int K = carm.n;
+    const size_t an = (size_t)h->HW * h->D * (aarm.per_image ? (size_t)batch : 1);      // weights of an anchored call
+    if (aarm.z) {          // an anchored call (rqamd_rqt_sample_anchor): refused here, before anything is enqueued
+        if (aarm.bad) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_anchor: null codebook or norms pointer");
+        for (int d = 0; d < h->D; ++d)
+            if ((uintptr_t)aarm.cb[d] & 15) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_anchor: codebook %d is not 16-byte aligned", d);
+        if (!aarm.weight) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_anchor: null weights");
+        if (K) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_anchor: an anchor together with rqamd_rqt_sample_compose");
+        if (fan) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_anchor: an anchor together with rqamd_rqt_sample_shared");
+        if (aarm.dim % 64 != 0 || aarm.dim < 64 || aarm.dim > 256) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_anchor: dim %d must be 64, 128, 192 or 256", aarm.dim);
+        for (int d = 0; d < h->D; ++d)
+            if (h->Vd[d] != h->V) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_anchor: depths with different vocabularies (vocab_sizes[%d] = %d < %d)", d, h->Vd[d], h->V);
+        for (size_t i = 0; i < an; ++i)
+            if (!(aarm.weight[i] >= 0.f) || !(aarm.weight[i] - aarm.weight[i] == 0.f))
+                return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_anchor: weight[%zu] must be finite and >= 0", i);
+    }
     if (K) {               // a composed call (rqamd_rqt_sample_compose): refused here, before anything is enqueued
         if (!guided) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_compose: extra conditions armed in front of an unguided call");
         if (fan) return rq_fail(RQAMD_ERR_UNSUPPORTED, "rqt_sample_compose: extra conditions together with rqamd_rqt_sample_shared (no group caches for the extra blocks)");
@@ -1168,6 +1228,38 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
         RQ_HIP(hipStreamSynchronize(st));
         h->cmp_host.assign(carm.weight, carm.weight + (size_t)K * batch);
         RQ_HIP(hipMemcpyAsync(h->cmp_w, h->cmp_host.data(), (size_t)K * batch * 4, hipMemcpyHostToDevice, st));
+    }
+    if (aarm.z) {
+        // the block of the three launches: first use, a larger batch or a wider z, outside any capture -- the anchored graphs hold the old
+        // addresses.  z: device copy on the stream; weights: host array -> staging block of the handle -> device table by an asynchronous
+        // copy ahead of the position loop (see row_host)
+        const size_t lrows = guided ? 2 * (size_t)batch : (size_t)batch;
+        if ((size_t)batch > h->anc_imgs || lrows > h->anc_lrows || (size_t)aarm.dim > h->anc_dim) {
+            const size_t ni = std::max(h->anc_imgs, (size_t)batch), nl = std::max(h->anc_lrows, lrows), nd = std::max(h->anc_dim, (size_t)aarm.dim);
+            h->anc_imgs = h->anc_lrows = h->anc_dim = 0;
+            const size_t bl = al(nl * h->V * 4), bd = al(ni * h->V * 4), br = al(ni * nd * 4), bp = al(ni * 64 * 4), bz = al(ni * h->HW * nd * 4),
+                         bw = al(ni * h->HW * h->D * 4);
+            RQ_TRY(h->anc_buf.reserve(bl + bd + br + 2 * bp + bz + bw));
+            char* q = (char*)h->anc_buf.p;
+            h->anc_logits = (float*)q; q += bl;
+            h->anc_dist = (float*)q; q += bd;
+            h->anc_resid = (float*)q; q += br;
+            h->anc_pv = (float*)q; q += bp;
+            h->anc_pi = (int*)q; q += bp;
+            h->anc_z = (float*)q; q += bz;
+            h->anc_w = (float*)q;
+            h->anc_imgs = ni; h->anc_lrows = nl; h->anc_dim = nd;
+            for (int f = 3 * rqamd_rqt::NFAM; f < 4 * rqamd_rqt::NFAM; ++f) h->gstale[f] = true;
+        }
+        RQ_HIP(hipStreamSynchronize(st));
+        // (one table per image in every case -- a shared table is repeated -- so that the captured fold launches hold ONE row stride and
+        //  calls with either kind of table replay the same graphs)
+        const size_t sn_w = (size_t)h->HW * h->D;
+        h->anc_host.resize((size_t)batch * sn_w);
+        for (int b = 0; b < batch; ++b) memcpy(h->anc_host.data() + b * sn_w, aarm.weight + (aarm.per_image ? b * sn_w : 0), sn_w * 4);
+        RQ_HIP(hipMemcpyAsync(h->anc_w, h->anc_host.data(), (size_t)batch * sn_w * 4, hipMemcpyHostToDevice, st));
+        RQ_HIP(hipMemcpyAsync(h->anc_z, aarm.z, (size_t)batch * h->HW * aarm.dim * 4, hipMemcpyDeviceToDevice, st));
+        c.anchor = true; c.acb = aarm.cb; c.acn = aarm.cn; c.adim = aarm.dim;
     }
     c.B = rows; c.codebooks = codebooks; c.temperature = temperature; c.top_k = top_k; c.top_p = top_p; c.sample = true;
     c.fan = fan;
@@ -1239,7 +1331,7 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
             t.T = (float*)q; t.tk = (int*)(q + tb); t.tp = (float*)(q + 2 * tb); t.gs = (float*)(q + 3 * tb); t.mp = (float*)(q + 4 * tb); t.typ = (float*)(q + 5 * tb);
             h->sch_image_rows = (size_t)batch;
             for (int f = rqamd_rqt::NFAM_SCHED0; f < rqamd_rqt::NFAM; ++f)
-                if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = h->gstale[f + rqamd_rqt::NFAM] = h->gstale[f + 2 * rqamd_rqt::NFAM] = true;
+                if ((f - rqamd_rqt::NFAM_SCHED0) & 2) h->gstale[f] = h->gstale[f + rqamd_rqt::NFAM] = h->gstale[f + 2 * rqamd_rqt::NFAM] = h->gstale[f + 3 * rqamd_rqt::NFAM] = true;
         }
         const rqamd_rqt::SchedTables& t = pi ? h->sch_image : h->sch_shared;
         RQ_HIP(hipMemcpyAsync(t.T, hT, nt * 4, hipMemcpyHostToDevice, st));
@@ -1258,6 +1350,10 @@ static int sample_impl(rqamd_rqt* h, const int64_t* partial, const uint8_t* keep
     rqamd_rqt::Key k{};
     k.B = rows; k.guided = guided ? 1 : 0; k.stream = stream; k.fan = fan; k.n_extra = K;
     for (int d = 0; d < h->D; ++d) k.cb[d] = codebooks[d];
+    if (aarm.z) {
+        for (int d = 0; d < h->D; ++d) { k.acb[d] = aarm.cb[d]; k.acn[d] = aarm.cn[d]; }
+        k.adim = aarm.dim;
+    }
     if (!rp && !sarm.on()) {       // (per-row and scheduled calls: no parameter value is in a captured launch, so none is in the key)
         k.T = temperature; k.gs = guided ? gscale : 0.f;
         for (int d = 0; d < h->D; ++d) { k.tk[d] = top_k[d]; k.tp[d] = top_p[d]; }
@@ -1420,6 +1516,23 @@ extern "C" int rqamd_rqt_sample_compose(rqamd_rqt* h, int n_extra, const int64_t
     h->carm.n = n_extra;
     for (int k = 0; k < n_extra; ++k) h->carm.cond[k] = extra_cond ? extra_cond[k] : nullptr;
     h->carm.weight = extra_weight;
+    return RQAMD_OK;
+}
+
+// Arms the next rqamd_rqt_sample / _masked / _guided / _rows call on the handle as an anchored call (include/rqamd.h): z (batch, H, W, dim)
+// fp32 DEVICE, D DEVICE pointers each to the codebooks (vocab codes of width dim) and their norms (the two pointer ARRAYS are copied
+// here), and HOST weights (H * W * D, or batch * H * W * D image-major with per_image = 1), read and checked by that call.  z NULL disarms.
+extern "C" int rqamd_rqt_sample_anchor(rqamd_rqt* h, const float* z, const float* const* codebooks, const float* const* code_norms, int dim,
+                                       const float* weight, int per_image) {
+    if (!h) return rq_fail(RQAMD_ERR_INVALID, "rqt_sample_anchor: null handle");
+    h->aarm = {};
+    if (!z) return RQAMD_OK;
+    h->aarm.z = z; h->aarm.dim = dim; h->aarm.weight = weight; h->aarm.per_image = per_image ? 1 : 0;
+    for (int d = 0; d < h->D; ++d) {
+        h->aarm.cb[d] = codebooks ? codebooks[d] : nullptr;
+        h->aarm.cn[d] = code_norms ? code_norms[d] : nullptr;
+        if (!h->aarm.cb[d] || !h->aarm.cn[d]) h->aarm.bad = 1;      // (refused by the armed call, which consumes the arming)
+    }
     return RQAMD_OK;
 }
 

@@ -196,6 +196,54 @@ struct ComposeArgs {
     float scale;
 };
 int rq_launch_compose(const ComposeArgs& a, hipStream_t s);
+
+// Anchored sampling (rqamd_rqt_sample_anchor, rqamd_anchor_logits): the logit of code v gets the quantiser's soft-code term of the residual
+// the anchored image has at this depth, x' = x - w * dist(r, codebook[v]), dist the fp32 squared distance of rq_launch_neg_distances.
+// Three rules are part of the contract.  l == -inf: LogitMask columns stay -inf.  w == 0: the logit stays bit for bit (fmaf(-0, dist, l)
+// would turn a -0.0 logit into +0.0, which the samplers' order keys tell apart).  A distance that is not finite -- NaN, or the +inf the
+// expanded form gives where an infinite component of z meets a code component of the other sign; a finite z row never has one -- leaves
+// the logit alone, so an image with a non-finite z row degrades to unanchored instead of to an all -inf row.
+// THE one place the anchor enters: the fold kernel of the engine and rqamd_anchor_logits call it (rqt_anchor.hip).
+static __device__ __forceinline__ float anchor_logit(float l, float dist, float w) {
+    const float inf = __int_as_float(0x7f800000);
+    return (l == -inf || w == 0.f || !(fabsf(dist) < inf)) ? l : fmaf(-w, dist, l);
+}
+
+// r[b][:] = z[b * z_stride + p * dim ..] - cb[0][c_0] - ... - cb[d-1][c_{d-1}], c_j = codes[b * code_stride + p * code_D + j], p = pos ? *pos : 0,
+// subtracted one depth after the other in fp32 as the quantiser does (resid_rows_kernel): stateless, recomputed from z at every depth.
+// Only codes of depths < d are read.  A code outside 0 .. K-1 traps, as rq_embed_kernel does.
+struct AnchorResidArgs {
+    const float* z;
+    long z_stride;          // floats between the rows of two images (engine: HW * dim; rows given one by one: dim)
+    const int64_t* codes;
+    long code_stride;       // codes between two images (engine: HW * D; rows given one by one: d)
+    int code_D;             // codes per position (engine: D)
+    const int* pos;         // device position counter, or null (position 0)
+    const float* cb[8];
+    int K;                  // codes per codebook
+    int d, dim, rows;       // dim % 4 == 0
+    float* out;             // [rows][dim]
+};
+int rq_launch_anchor_resid(const AnchorResidArgs& a, hipStream_t s);
+
+// out_c[r][v] = anchor_logit(c[r][v], dist[r][v], w_r), and with u non-null out_u[r][v] = anchor_logit(u[r][v], dist[r][v], w_r): the twins of a
+// guided pair get the same term, so guide_logit(c', u', s) is the guided mix minus w * dist up to rounding.
+// w_r = w[r * w_row_stride + (pos ? *pos : 0) * D + d], a workgroup-uniform load.
+struct AnchorFoldArgs {
+    const float *c, *u;     // [rows][V]; u null: unguided
+    const float* dist;      // [rows][V]
+    const float* w;         // device
+    long w_row_stride;      // 0: one table for all rows
+    const int* pos;         // device position counter, or null
+    int D, d;
+    int rows, V;
+    float *out_c, *out_u;   // [rows][V]; out_u with u
+};
+int rq_launch_anchor_fold(const AnchorFoldArgs& a, hipStream_t s);
+// the three stages of one anchored step over `rows` rows: residual -> resid, distances -> dist (part_v / part_i: rows * 64 each), fold
+int rq_launch_anchor_step(const AnchorResidArgs& r, const float* codebook, const float* code_norms, float* dist, float* part_v, int* part_i,
+                          const AnchorFoldArgs& f, hipStream_t s);
+
 int rq_launch_sample_sched(const SampleArgs& a, hipStream_t s);     // rqt_sample_sched.hip
 // is a filter of the TRUNC instantiations in effect (scalars), or could one be (tables)?
 static inline bool rq_sample_trunc_on(const SampleArgs& a) {

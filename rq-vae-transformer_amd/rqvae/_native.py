@@ -103,6 +103,9 @@ _SIGS = {
     'rqamd_rqt_sample_shared': (C.c_int, [C.c_void_p, C.c_int]),
     'rqamd_rqt_sample_compose': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'rqamd_compose_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    'rqamd_rqt_sample_anchor': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    'rqamd_anchor_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'rqamd_rqt_kv_bytes': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_graph_captures': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     'rqamd_rqt_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
@@ -535,6 +538,57 @@ def compose_logits(c, u, extras, weights, scale):
     return out
 
 
+ANCHOR_DIMS = (64, 128, 192, 256)
+
+
+def anchor_logits(logits, z_rows, codes, codebooks, norms, weight, logits_u=None, want_resid=False, want_dist=False):
+    """rqamd_anchor_logits: the three stages of ONE anchored sampling step over given rows (include/rqamd.h: rqamd_rqt_sample_anchor) --
+    the residual r = z_rows - codebooks[0][codes[:, 0]] - ... of depth d = codes.shape[1] in the quantiser's order and bits, its distances
+    to codebooks[d] (the values of rq_distances), and logits - weight * dist through the device function of the engine's fold.
+    logits (rows, vocab) fp32; z_rows (rows, dim) fp32; codes (rows, d) int64 (d = 0: depth 0; None is (rows, 0)); codebooks / norms:
+    at least d + 1 tensors (vocab, dim) / (vocab,); weight (rows,) fp32 on the device; logits_u: the unconditional twins or None.
+    -> out, or (out, out_u) with logits_u; want_resid / want_dist append the (rows, dim) residual / the (rows, vocab) distances."""
+    if logits.dim() != 2 or (logits_u is not None and tuple(logits_u.shape) != tuple(logits.shape)):
+        raise ValueError(f'anchor_logits: logits of shape {tuple(logits.shape)}' + ('' if logits_u is None else f' and {tuple(logits_u.shape)}')
+                         + '; expected (rows, vocab)')
+    rows, vocab = logits.shape
+    if z_rows.dim() != 2 or z_rows.shape[0] != rows:
+        raise ValueError(f'anchor_logits: z_rows of shape {tuple(z_rows.shape)}; expected ({rows}, dim)')
+    dim = z_rows.shape[1]
+    if dim not in ANCHOR_DIMS:
+        raise NotImplementedError(f'anchor_logits: dim {dim} must be 64, 128, 192 or 256')
+    d = 0 if codes is None else codes.shape[-1]
+    if codes is not None and (codes.dim() != 2 or codes.shape[0] != rows):
+        raise ValueError(f'anchor_logits: codes of shape {tuple(codes.shape)}; expected ({rows}, d)')
+    if len(codebooks) <= d or len(norms) <= d:
+        raise ValueError(f'anchor_logits: {len(codebooks)} codebooks / {len(norms)} norms for depth {d}')
+    for cb, cn in zip(codebooks[:d + 1], norms[:d + 1]):
+        if tuple(cb.shape) != (vocab, dim) or tuple(cn.shape) != (vocab,):
+            raise ValueError(f'anchor_logits: codebook of shape {tuple(cb.shape)} with norms {tuple(cn.shape)}; expected ({vocab}, {dim}) and ({vocab},)')
+    if tuple(weight.shape) != (rows,):
+        raise ValueError(f'anchor_logits: weight of shape {tuple(weight.shape)}; expected ({rows},)')
+    logits, z_rows, weight = logits.contiguous(), z_rows.contiguous(), weight.contiguous()
+    logits_u = None if logits_u is None else logits_u.contiguous()
+    codes = None if d == 0 else codes.to(torch.long).contiguous()
+    out = torch.empty_like(logits)
+    out_u = None if logits_u is None else torch.empty_like(logits)
+    resid = torch.empty((rows, dim), dtype=torch.float32, device=logits.device) if want_resid else None
+    dist = torch.empty((rows, vocab), dtype=torch.float32, device=logits.device) if want_dist else None
+    if rows == 0:
+        res = (out,) if logits_u is None else (out, out_u)
+        res += ((resid,) if want_resid else ()) + ((dist,) if want_dist else ())
+        return res[0] if len(res) == 1 else res
+    ws = torch.empty((rows * 512 + 256 + rows * dim * 4 + 256 + rows * vocab * 4,), dtype=torch.uint8, device=logits.device)
+    cbs, nrm = _ptr_array(list(codebooks[:d + 1])), _ptr_array(list(norms[:d + 1]))
+    with on_device_of(logits):
+        check(lib().rqamd_anchor_logits(ptr(logits, torch.float32), ptr(logits_u, torch.float32), ptr(z_rows, torch.float32), ptr(codes, torch.int64),
+                                        cbs, nrm, d, dim, vocab, ptr(weight, torch.float32), rows, ptr(out), ptr(out_u), ptr(resid), ptr(dist),
+                                        ptr(ws), ws.numel(), stream_of(logits)))
+    res = (out,) if logits_u is None else (out, out_u)
+    res += ((resid,) if want_resid else ()) + ((dist,) if want_dist else ())
+    return res[0] if len(res) == 1 else res
+
+
 def dbg_gemm(a_bf16, w_bf16, bias=None, epi=3, bm=0, bn=0, splitk=0, out=None):
     """diagnostics: out[M,N] = a[M,K] @ w[N,K]^T (+bias); a, w are torch.bfloat16."""
     M, K = a_bf16.shape
@@ -899,6 +953,40 @@ class RqtEngine(_Engine):
             parr[i] = None if t is None else ptr(t, torch.int64).value
         return K, parr, (C.c_float * (K * B))(*w), conds
 
+    def arm_anchor(self, z=None, codebooks=None, norms=None, weight=None, per_image=False):
+        """rqamd_rqt_sample_anchor for the NEXT sample / sample_masked / sample_guided / sample_rows call of this object: anchored sampling.
+        `z` (B, H, W, dim) fp32 on the engine's device; `codebooks` / `norms`: D tensors (vocab_size, dim) / (vocab_size,) each; `weight`:
+        a flat host sequence or tensor of H * W * D values >= 0 (per_image: B * H * W * D, image-major, depth last).  z None disarms.
+        Checked when the call is made, before the library is called."""
+        self._anchor = None if z is None else (z, list(codebooks), list(norms), weight, bool(per_image))
+
+    def _anchor_arrays(self, B):
+        """the arming of arm_anchor as the arguments of rqamd_rqt_sample_anchor, checked (ValueError / NotImplementedError), and consumed"""
+        anc, self._anchor = getattr(self, '_anchor', None), None
+        if anc is None:
+            return None
+        z, cbs, norms, weight, per_image = anc
+        c = self.cfg
+        if z.dim() != 4 or tuple(z.shape[:3]) != (B, c.H, c.W) or z.dtype != torch.float32:
+            raise ValueError(f'anchor: z of shape {tuple(z.shape)} / {z.dtype}; expected ({B}, {c.H}, {c.W}, dim) / torch.float32')
+        dim = z.shape[3]
+        if dim not in ANCHOR_DIMS:
+            raise NotImplementedError(f'anchor: dim {dim} must be 64, 128, 192 or 256')
+        if len(cbs) < c.D or len(norms) < c.D:
+            raise ValueError(f'anchor: {len(cbs)} codebooks / {len(norms)} norms for depth {c.D}')
+        for cb, cn in zip(cbs[:c.D], norms[:c.D]):
+            if tuple(cb.shape) != (c.vocab_size, dim) or tuple(cn.shape) != (c.vocab_size,):
+                raise ValueError(f'anchor: codebook of shape {tuple(cb.shape)} with norms {tuple(cn.shape)}; expected ({c.vocab_size}, {dim}) '
+                                 f'and ({c.vocab_size},)')
+        self._on_my_device(z, *cbs[:c.D], *norms[:c.D])
+        w = torch.as_tensor(weight, dtype=torch.float32, device='cpu').reshape(-1).contiguous()
+        n = c.H * c.W * c.D * (B if per_image else 1)
+        if w.numel() != n:
+            raise ValueError(f'anchor: {w.numel()} weights; expected {n}')
+        z = z.contiguous()
+        # (the tensors and arrays the library reads, alive until the call returns)
+        return z, _ptr_array(cbs[:c.D]), _ptr_array(norms[:c.D]), dim, w, int(per_image), cbs, norms
+
     def kv_bytes(self):
         """device bytes currently reserved for the KV caches of the handle (rqamd_rqt_kv_bytes)"""
         n = C.c_int64()
@@ -932,9 +1020,17 @@ class RqtEngine(_Engine):
         fan, self._shared = getattr(self, '_shared', 0), 0
         try:
             comp = self._compose_arrays(partial.shape[0])
+            anc = self._anchor_arrays(partial.shape[0])
         except Exception:
-            self._trunc = self._sched = None
+            self._trunc = self._sched = self._anchor = None
             raise
+        if anc is not None:
+            unanchored = call
+
+            def call(anc=anc):
+                rc = self._L.rqamd_rqt_sample_anchor(self._h, ptr(anc[0], torch.float32), anc[1], anc[2], anc[3],
+                                                     C.cast(anc[4].data_ptr(), C.c_void_p), anc[5])
+                return rc if rc != 0 else unanchored()
         if comp is not None:
             if not guided:
                 raise ValueError('extra conditions armed in front of an unguided call')

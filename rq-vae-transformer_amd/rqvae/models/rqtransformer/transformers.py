@@ -94,6 +94,29 @@ def _shared_prompt(fn):
     return shared
 
 
+def _anchored(fn):
+    """sample() / sample_guided() inside ``with self.anchor(z, weight)``: the checks of anchored sampling, made before anything runs, and
+    the mark that makes _sampling_eng() arm the engine (rqamd_rqt_sample_anchor) and the host loops fold the anchor into their logits for
+    the duration of this call only."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def anchored(self, *args, **kwargs):
+        if self._anchor is None or self._anchor_live is not None:
+            return fn(self, *args, **kwargs)
+        a = sig.bind(self, *args, **kwargs)
+        a.apply_defaults()
+        a = a.arguments
+        self._anchor_live = self._anchor_args(a['partial_sample'], a['model_aux'])
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            self._anchor_live = None
+            for eng, _ in self._engines.values():
+                eng.arm_anchor(None)                  # (a call refused before it reached the library leaves nothing armed)
+    return anchored
+
+
 def _negative_prompt(fn):
     """sample_guided() also takes ``negative=`` / ``negative_scale=`` as keywords: the call then runs inside
     ``self.extra_conds(conds=[negative], weights=[-negative_scale])`` (see extra_conds()); both the keyword and the context: ValueError.
@@ -196,6 +219,8 @@ class RQTransformer(Stage2Model):
         self._shared_cond = 0                            # images per prompt of the sample() calls inside `with self.shared_cond(n)`
         self._shared_live = 0                            # ... while such a call runs (_shared_prompt)
         self._extra_conds = None                         # (conds, weights) of the sample_guided() calls inside `with self.extra_conds(...)`
+        self._anchor = None                              # (z, weight) of the sample() calls inside `with self.anchor(...)`
+        self._anchor_live = None                         # ... checked and broadcast, while such a call runs (_anchored)
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -269,6 +294,9 @@ class RQTransformer(Stage2Model):
             eng._kept_runs_one_pass = want_runs
         if self._shared_live:
             eng.arm_shared(self._shared_live)           # the next sampling call of the engine is a shared-prompt call
+        if self._anchor_live is not None:               # ... an anchored call (the host loops never reach it: _anchored disarms)
+            a = self._anchor_live
+            eng.arm_anchor(a['z'], a['cbs'], a['norms'], a['w'].reshape(-1), a['per_image'])
         return eng
 
     def _cond_rows(self, B):
@@ -470,6 +498,7 @@ class RQTransformer(Stage2Model):
 
     @_truncation_keywords
     @_shared_prompt
+    @_anchored
     @torch.no_grad()
     def sample(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, keep_mask=None):
@@ -765,6 +794,106 @@ class RQTransformer(Stage2Model):
             out[idx] = _native.compose_logits(cu[:n][idx], cu[n:][idx], x[:, idx], W[:, idx], s)
         return out
 
+    # ------------------------------------------------------------------ anchored sampling
+    @contextlib.contextmanager
+    def anchor(self, z, weight=1.0):
+        """Anchored sampling (not in the reference): the sample() / sample_guided() calls made inside the block draw codes near an encoded
+        image -- variations of an image, img2img with a strength knob, soft inpainting.  ``z``: the output of ``model_aux.encode(images)``,
+        (B, H, W, input_embed_dim) fp32; None is the plain call.  At every step the logits of image b get the quantiser's own soft-code
+        term for the residual the image has at that depth given the codes drawn so far,
+
+            x'[v] = x[v] - w(b, p, d) * dist(r_d(b, p), codebook_d[v]),    r_0 = z[b, p],   r_{d+1} = r_d - codebook_d[code(b, p, d)]
+
+        with dist the quantiser's squared distance in fp32: w = 0 is the prior, w -> inf is ``model_aux.get_codes(images)``, and in
+        between every code is drawn from p_model * softmax(-dist / temp) with w = 1 / temp, ``get_soft_codes`` used as a likelihood.
+        ``weight`` (>= 0, finite): a float; a sequence of D per-depth values (keep the layout -- depth 0 or 1 -- and redraw the detail,
+        or the reverse); or a tensor of shape (B,), (B, D), (H, W) (a soft inpainting mask), (H, W, D) or (B, H, W, D).  Codebooks and
+        norms come from ``model_aux``, as for soft_target_loss(z_e=...).  The loop runs inside the engine (rqamd_rqt_sample_anchor): three
+        more launches per step, captured graphs of their own whose keys hold no z and no weight; filters, temperature and Philox
+        counters are those of the plain call, and weight 0 returns its codes bit for bit.  An image whose z holds a NaN or an inf
+        degrades to unanchored.  Composes with keep_mask (the residual follows the kept code), start_loc, prefix_mode / kept_run_mode,
+        per-image tensors, seeds(), truncation(), schedule(), guidance, amp and return_log_probs() (draw: under the anchored
+        distribution after all stages; model / model_uncond: the raw logits); ``cached=False`` is the host loop over
+        _native.anchor_logits, bit for bit equal to ``cached=True``.  shared_cond(), extra_conds(), ``sampler='torch'``, depths with
+        different vocabularies and a z width other than 64 / 128 / 192 / 256 raise NotImplementedError; a wrong shape or a negative or
+        non-finite weight raises ValueError, before anything runs."""
+        saved, self._anchor = self._anchor, None if z is None else (z, weight)
+        try:
+            yield self
+        finally:
+            self._anchor = saved
+
+    def _anchor_args(self, partial_sample, model_aux):
+        """self._anchor for the images of `partial_sample`, checked -> dict(z= (B, H, W, dim) fp32 on the device, cbs= / norms= D tensors,
+        w= (1 or B, H*W, D) fp32 on the host, per_image=, w_dev= (B, H*W, D) on the device for the host loops)"""
+        z, weight = self._anchor
+        (H, W, D) = self.block_size
+        B, device = partial_sample.shape[0], partial_sample.device
+        if self.sampler == 'torch':
+            raise NotImplementedError("anchor() runs in the on-device sampler; sampler='torch' has no anchored form")
+        if self._shared_cond:
+            raise NotImplementedError('anchor() inside shared_cond(): rqamd_rqt_sample_anchor together with rqamd_rqt_sample_shared is not built')
+        if self._extra_conds is not None:
+            raise NotImplementedError('anchor() inside extra_conds(): rqamd_rqt_sample_anchor together with rqamd_rqt_sample_compose is not built')
+        V = max(self.vocab_size)
+        if any(v != V for v in self.vocab_size):
+            raise NotImplementedError(f'anchor(): depths with different vocabularies ({list(self.vocab_size)}); one codebook size is needed')
+        if model_aux is None or not hasattr(model_aux, 'quantizer'):
+            raise ValueError('anchor() needs model_aux, the RQVAE whose encoder produced z and whose quantiser holds the codebooks')
+        quantizer = model_aux.quantizer
+        if not torch.is_tensor(z) or z.dim() != 4:
+            raise ValueError(f'anchor: z of shape {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}; expected ({B}, {H}, {W}, dim)')
+        try:
+            z = quantizer.to_code_shape(z.detach()).to(device=device, dtype=torch.float32).contiguous()
+        except RuntimeError:
+            raise ValueError(f'anchor: z of shape {tuple(z.shape)} does not fold into the code shape ({B}, {H}, {W}, dim)') from None
+        if tuple(z.shape[:3]) != (B, H, W):
+            raise ValueError(f'anchor: z of shape {tuple(z.shape)}; expected ({B}, {H}, {W}, dim)')
+        dim = z.shape[3]
+        if dim not in _native.ANCHOR_DIMS:
+            raise NotImplementedError(f'anchor: dim {dim} must be 64, 128, 192 or 256')
+        cbs, norms = quantizer.codebook_list()[:D], quantizer._norm_list()[:D]
+        if len(cbs) < D:
+            raise ValueError(f'model_aux has {len(cbs)} codebooks, the transformer needs {D}')
+        for d, cb in enumerate(cbs):
+            if tuple(cb.shape) != (V, dim):
+                raise ValueError(f'anchor: codebook {d} has shape {tuple(cb.shape)}; expected ({V}, {dim})')
+        if torch.is_tensor(weight):
+            t = weight.detach().cpu()
+            if t.dtype.is_complex or t.dtype == torch.bool:
+                raise ValueError(f'anchor: weight of dtype {t.dtype}; expected real values')
+            t, shp = t.to(torch.float32), tuple(weight.shape)
+            forms = {(): (1, 1, 1), (B,): (B, 1, 1), (B, D): (B, 1, D), (H, W): (1, H * W, 1), (H, W, D): (1, H * W, D), (B, H, W, D): (B, H * W, D)}
+            if shp not in forms:
+                raise ValueError(f'anchor: weight of shape {shp}; expected {(B,)}, {(B, D)}, {(H, W)}, {(H, W, D)} or {(B, H, W, D)}')
+            if (B, D) == (H, W) and shp == (B, D):
+                raise ValueError(f'anchor: weight of shape {shp} is both (B, D) and (H, W) here; pass it as {(B, H, W, D)}')
+            t = t.reshape(forms[shp])
+        elif isinstance(weight, (int, float)) and not isinstance(weight, bool):
+            t = torch.full((1, 1, 1), float(weight), dtype=torch.float32)
+        else:
+            vals = [float(v) for v in weight]
+            if len(vals) != D:
+                raise ValueError(f'anchor: {len(vals)} weights; expected a number, one value per depth ({D}) or a tensor')
+            t = torch.tensor(vals, dtype=torch.float32).reshape(1, 1, D)
+        if not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+            raise ValueError('anchor: every weight must be finite and >= 0')
+        per_image = t.shape[0] > 1
+        w = t.expand(B if per_image else 1, H * W, D).contiguous()
+        return dict(z=z, cbs=cbs, norms=norms, w=w, per_image=per_image, w_dev=w.expand(B, H * W, D).to(device))
+
+    def _anchor_step(self, logits, xs, n, pos, d, guided):
+        """host loops: the logits of step (pos, d) with the anchor of this call folded in (_native.anchor_logits: the engine's three
+        launches over the n images) -- both halves of a guided step; unchanged outside anchor()"""
+        a = self._anchor_live
+        if a is None:
+            return logits
+        h, w = divmod(pos, self.block_size[1])
+        z_rows, codes, wt = a['z'][:, h, w], xs[:n, h, w, :d], a['w_dev'][:, pos, d]
+        if guided:
+            return torch.cat(_native.anchor_logits(logits[:n], z_rows, codes, a['cbs'], a['norms'], wt, logits_u=logits[n:2 * n]))
+        return _native.anchor_logits(logits, z_rows, codes, a['cbs'], a['norms'], wt)
+
     # ------------------------------------------------------------------ per-image sampling parameters
     @contextlib.contextmanager
     def shared_cond(self, n):
@@ -945,6 +1074,7 @@ class RQTransformer(Stage2Model):
     @_negative_prompt
     @_truncation_keywords
     @_shared_prompt
+    @_anchored
     @torch.no_grad()
     def sample_guided(self, partial_sample, model_aux=None, cond=None, start_loc=(0, 0), temperature=1.0, top_k=None, top_p=None,
                       amp=False, cached=True, is_tqdm=False, desc="Sampling", fast=True, *, uncond=None, guidance_scale=1.0,
@@ -1238,6 +1368,7 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(device, lambda: eng.logits(xs2, c2, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
+                logits = self._anchor_step(logits, xs2, B, pos, d, guided)
                 if comp is not None:
                     logits = self._compose_rows(logits, B, comp, G[:, pos, d].tolist())
                 elif guided:
@@ -1319,6 +1450,7 @@ class RQTransformer(Stage2Model):
                 logits = self._on_side_stream(xs.device, lambda: eng.logits(xs, cond, cbs))[:, h, w, d].contiguous()
                 if self.vocab_size[d] < logits.shape[-1]:
                     logits[:, self.vocab_size[d]:] = float('-inf')          # LogitMask, as the sampling path applies it
+                logits = self._anchor_step(logits, xs, n, pos, d, guidance_scale is not None)
                 if comp is not None:
                     logits = self._compose_rows(logits, n, comp, guidance_scale)
                 elif guidance_scale is not None and rows is not None:
